@@ -12,7 +12,13 @@ Modes
   fused (default): fs_step_n, `--chunk` ticks per kernel launch, every tick's
                    outputs kept in a [chunk][N] rollout buffer in HBM.
   step:            fs_step, one kernel launch per tick (the VectorEnv.step path).
-Both modes are timed and reported; `value` is the --mode one.
+`value` is the --mode one.
+
+A plain run sets up, warms up, times exactly `--steps` steps (one region; `--regions R` times R
+of them and reports the median), writes the last step's outputs if `--dump-outputs DIR` is given
+and prints the line.  `--full` adds everything else the line can hold: the other mode and
+trajectory layout, the host-action and gather legs, the roofline block, c4_strong, the C2 / C5 /
+VectorEnv legs and the CPU baseline (five regions by default).
 
 Multi-GPU: one process per GPU, arenas sharded per rank with no data-path collective
 (`scaling: weak`); max-over-ranks timing.  `python bench.py --gpus N` starts the N ranks
@@ -43,6 +49,9 @@ STEP_IO_BYTES = 40
 PACKED_STEP_MOVED_BYTES = 42  # 2 B in + 40 B out per env-step in the packed layout (incl. the pad)
 XGMI_LINK_GBPS = 153.0  # per xGMI link and direction (task brief: 7 links x ~153 GB/s per MI355X)
 LEG_TICKS = 1000        # ticks per region (and per launch) of the fused side legs, whatever --steps is
+# most HBM the resident action rows (both players) take: 2^31 elements per fs_hash_actions call, half of
+# what its one-thread-per-element launch could cover (a 2^32-thread grid is refused)
+ACTION_BYTES = 4 << 30
 VENV_STEPS = 200        # timed FootsiesVectorEnv steps, after a warm-up into steady state
 
 
@@ -80,8 +89,17 @@ def parse():
     ap.add_argument("--cpu-seconds", type=float, default=10.0, help="target length of the cpu_baseline sample")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--kernel-samples", type=int, default=50, help="launches timed back-to-back for roofline")
-    ap.add_argument("--regions", type=int, default=5,
-                    help="timed regions of exactly --steps steps each, back to back; value = the median region")
+    ap.add_argument("--regions", type=int, default=None,
+                    help="timed regions of exactly --steps steps each, back to back; value = the median region "
+                         "(default: 1, so --steps is the number of timed steps; 5 with --full)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure everything else the line can report: the other mode and "
+                         "trajectory layout, the host-action and gather legs (in a one-rank RCCL group at one GPU), "
+                         "the roofline block, c4_strong, the C2 / C5 / VectorEnv legs and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path's last step returned (the last launch's "
+                         "trajectory in fused mode, the bound outputs in step mode) as DIR/<name>.npy, float32 / "
+                         "float64, a fixed seeded sample of at most 64 MB")
     ap.add_argument("--roofline-ticks", type=int, default=1000,
                     help="ticks per fs_step_n launch of the roofline block (the shape profiles/ covers)")
     ap.add_argument("--no-extras", action="store_true", help="skip the C2 bot-opponent and C5 policy-loop rates")
@@ -467,6 +485,59 @@ def short_launch_attribution(ticks):
     return dict(doc["critical_path"], span_us=doc["span_us"], source=os.path.relpath(paths[-1], ROOT))
 
 
+DUMP_ARENAS = 256      # --dump-outputs: arenas sampled for every kept tick of the last launch
+DUMP_TICKS = 1024      # ... of its last this many ticks
+DUMP_LAST_ARENAS = 65536  # ... and arenas kept of its last tick (all of them at the C3 size)
+
+
+def dump_outputs(path, fields, ticks, seed):
+    """--dump-outputs: the outputs of the timed path's last step as path/<name>.npy, float32
+    (reward: float64; every integer field is below 2^24, so the conversion is exact).
+    `fields` maps alloc_trajectory's names to [rows][N](,2) arrays (device tensors or numpy)
+    whose first `ticks` rows the last launch wrote, or to [N](,2) arrays (ticks = None, step
+    mode: the bound outputs after the last step).  Kept, about 40 MB at the default shape:
+    * traj_<name>: the last min(ticks, DUMP_TICKS) ticks of DUMP_ARENAS arenas (a sorted sample
+      drawn from --seed, listed in traj_arena_index), [ticks][arenas](,2);
+    * last_<name>: the last tick of up to DUMP_LAST_ARENAS arenas (last_arena_index), [arenas](,2).
+    final_* rows of arenas that did not end the tick are left as they were by the kernels, so
+    they are written as zeros here."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    n = next(iter(fields.values())).shape[0 if ticks is None else 1]
+    rng = np.random.default_rng(int(seed) & 0xFFFFFFFF)
+    traj_idx = np.sort(rng.choice(n, min(n, DUMP_ARENAS), replace=False))
+    last_idx = np.arange(n) if n <= DUMP_LAST_ARENAS else np.sort(rng.choice(n, DUMP_LAST_ARENAS, replace=False))
+
+    def host(a, rows, idx):
+        if rows is not None:
+            a = a[rows]
+        axis = 1 if isinstance(rows, slice) else 0
+        if isinstance(a, np.ndarray):
+            return np.take(a, idx, axis=axis)
+        import torch
+        return a.index_select(axis, torch.as_tensor(idx, device=a.device)).cpu().numpy()
+
+    def ended(rows, idx):
+        return (host(fields["terminated"], rows, idx) | host(fields["truncated"], rows, idx)).astype(bool)
+
+    def save(name, a, done):
+        if name.split("_", 1)[1].startswith("final_"):
+            a = np.where(done if a.ndim == done.ndim else done[..., None], a, 0)
+        np.save(os.path.join(path, name + ".npy"), a.astype(np.float64 if a.dtype == np.float64 else np.float32))
+
+    last = None if ticks is None else ticks - 1
+    done = ended(last, last_idx)
+    for name, a in fields.items():
+        save("last_" + name, host(a, last, last_idx), done)
+    np.save(os.path.join(path, "last_arena_index.npy"), last_idx.astype(np.float64))
+    if ticks is not None:
+        rows = slice(max(0, ticks - DUMP_TICKS), ticks)
+        done = ended(rows, traj_idx)
+        for name, a in fields.items():
+            save("traj_" + name, host(a, rows, traj_idx), done)
+        np.save(os.path.join(path, "traj_arena_index.npy"), traj_idx.astype(np.float64))
+
+
 def dry_run(args, world, rank):
     """The multi-rank plumbing without a GPU: the same regions (barrier on both sides, host wall
     clock, max over ranks), a no-op CPU step, one JSON line from rank 0 marked dry_run."""
@@ -519,6 +590,8 @@ def main():
     args = parse()
     if args.gpus is not None and args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1:
+        raise SystemExit("--steps must be >= 1")
     if args.gpus is not None and args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # the driver's plain `python3 bench.py --gpus N`: start the N ranks (nothing has touched the GPU)
         sys.exit(launch_ranks(args))
@@ -528,6 +601,8 @@ def main():
     if args.gpus is not None and world != args.gpus:
         raise SystemExit("bench.py --gpus %d, but the launcher started %d rank(s) (WORLD_SIZE)" % (args.gpus, world))
     args.gpus = world
+    if args.regions is None:
+        args.regions = 5 if args.full else 1
     if args.dry_run:
         return dry_run(args, world, rank)
     import torch
@@ -547,9 +622,9 @@ def main():
             dist.init_process_group("nccl", device_id=torch.device("cuda", local))
         else:
             dist.init_process_group("gloo")
-    elif args.dist_backend == "nccl" and not args.no_solo_group:
-        # the plain one-GPU run (the driver's `bench.py --gpus 1`) joins a one-rank RCCL group too, so
-        # the per-step gather legs run their collective at N = 1 as well (RCCL's own kernels and
+    elif args.full and args.dist_backend == "nccl" and not args.no_solo_group:
+        # the one-GPU --full run without a launcher joins a one-rank RCCL group too, so the
+        # per-step gather legs run their collective at N = 1 as well (RCCL's own kernels and
         # copies at world size 1); a failure to form it leaves the run ungrouped and says so
         torch.cuda.set_device(local)
         try:
@@ -564,7 +639,7 @@ def main():
 
     from footsies_gym_amd import _abi
     from footsies_gym_amd._lib import check, lib, library_info
-    from footsies_gym_amd.simulator import FootsiesSim
+    from footsies_gym_amd.simulator import FootsiesSim, unpack_trajectory
 
     N, K, W = args.envs, args.steps, args.warmup
     if args.global_envs:
@@ -579,9 +654,12 @@ def main():
     L = lib()
     # synthetic inputs resident in HBM before timing: W warm-up rows, then R regions of K rows
     R = max(1, args.regions)
-    p1, p2 = sim.hash_actions(W + R * K, seed=args.seed, t0=0)
-    torch.cuda.synchronize(dev)
     chunk = max(1, min(args.chunk, K))
+    # (a long run keeps at most ACTION_BYTES of rows resident and reads them round and round: a
+    # launch whose rows would pass the end of the table starts at its first row instead)
+    rows_total = max(chunk, min(W + R * K, ACTION_BYTES // (2 * N)))
+    p1, p2 = sim.hash_actions(rows_total, seed=args.seed, t0=0)
+    torch.cuda.synchronize(dev)
     packed = args.layout == "packed"
     alloc = sim.alloc_packed_trajectory if packed else sim.alloc_trajectory
     traj = alloc(chunk)  # zero-filled: the pages are resident before timing
@@ -602,6 +680,7 @@ def main():
         # synchronizes only (building them inline cost ~0.9 us per 20-tick region,
         # profiles/r05ag_region_args.txt).
         rows = a1.shape[0]
+        assert rows >= ticks_per_launch, (rows, ticks_per_launch)  # (a launch never reads past the table)
         q1 = [C.c_void_p(b1 + k * N) for k in range(rows)]
         q2 = [C.c_void_p(b2 + k * N) for k in range(rows)]
         tdr = C.byref(td)
@@ -609,7 +688,7 @@ def main():
 
         def run_step(k0, n):
             for k in range(k0, k0 + n):
-                rc = fs_step(h, q1[k], q2[k], act)
+                rc = fs_step(h, q1[k % rows], q2[k % rows], act)
                 if rc:
                     check(rc, h)
 
@@ -617,10 +696,13 @@ def main():
             k = k0
             while k < k0 + n:
                 m = min(ticks_per_launch, k0 + n - k)
+                o = k % rows
+                if o + m > rows:
+                    o = 0
                 if packed:
-                    rc = fs_step_n_packed(h, m, q1[k], q2[k], tdr)
+                    rc = fs_step_n_packed(h, m, q1[o], q2[o], tdr)
                 else:
-                    rc = fs_step_n(h, m, q1[k], q2[k], 0, tdr)
+                    rc = fs_step_n(h, m, q1[o], q2[o], 0, tdr)
                 if rc:
                     check(rc, h)
                 k += m
@@ -699,10 +781,14 @@ def main():
         (run_fused if args.mode == "fused" else run_step)(0, W)
     torch.cuda.synchronize(dev)
 
-    # R back-to-back regions of exactly K steps each (fresh action rows per region); the
+    # R back-to-back regions of exactly K steps each (fresh action rows per region while the
+    # resident table holds them all, config.action_rows; a longer run reads it again); the
     # median region is reported, every region's wall time is listed
     res = {}
-    for mode, fn in (("fused", run_fused), ("step", run_step)):
+    other = "step" if args.mode == "fused" else "fused"
+    # (the --mode one first, so its last step's outputs are the same with and without --full's other mode)
+    for mode in (args.mode, other) if args.full else (args.mode,):
+        fn = run_fused if mode == "fused" else run_step
         local_walls = []
         walls = [timed(fn, W + r * K, K) for r in range(R)]
         wall = sorted(walls)[len(walls) // 2]
@@ -710,6 +796,57 @@ def main():
         res[mode] = {"wall_s": wall, "region_walls_ms": [round(1e3 * w, 4) for w in walls],
                      "env_steps_per_s": world * N * K / wall, "ms_per_step": 1e3 * wall / K,
                      "rank_walls_ms": rank_values(mine)}
+        if mode == args.mode and args.dump_outputs and rank == 0:
+            # what the last timed step handed back, before anything else runs on this handle: the
+            # last launch's ticks of the trajectory (fused), the bound outputs (step)
+            if mode == "fused":
+                last_ticks = K - ((K - 1) // chunk) * chunk
+                dump_outputs(args.dump_outputs, unpack_trajectory(traj) if packed else traj, last_ticks, args.seed)
+            else:
+                dump_outputs(args.dump_outputs, sim.outputs_numpy(), None, args.seed)
+    out = {
+        "metric": METRIC,
+        "value": res[args.mode]["env_steps_per_s"],
+        "unit": "env-steps/s",
+        "n_gpus": world,
+        "steps": K,
+        "warmup": W,
+        "ms_per_step": res[args.mode]["ms_per_step"],
+        "higher_is_better": True,
+        "scaling": scaling,
+        "vs_baseline": None,
+        "dtype": "int32+f32 (reward f64)",
+        "data": "synthetic (splitmix64 self-play actions in HBM)" + (
+            "" if rows_total >= W + R * K else "; the %d resident rows are read again after the last" % rows_total),
+        "library": library_info(),
+        "config": {"workload": ("C4 strong: %d arenas over %d GPUs" % (N * world, world) if args.global_envs else
+                                "C3: %d arenas/GPU" % N) + ", self-play random actions, P2 external, auto-reset same-step",
+                   "envs_per_gpu": N, "global_envs": N * world, "mode": args.mode,
+                   "ticks_per_launch": chunk if args.mode == "fused" else 1,
+                   "trajectory": ("packed records (fs_step_n_packed)" if packed else "one array per field (fs_step_n)")
+                   if args.mode == "fused" else None, "parallelism": "arena-shard x%d" % world,
+                   # the resident action rows and the rows the run steps through: repeated when fewer
+                   "action_rows": rows_total, "action_rows_needed": W + R * K,
+                   "action_rows_repeat": rows_total < W + R * K},
+        "ranks": {"world_size": dist.get_world_size() if grouped else 1,
+                  "backend": dist.get_backend() if grouped else None,
+                  "launcher": "WORLD_SIZE" in os.environ, "solo_group_error": solo_group_error,
+                  "rank_walls_ms": res[args.mode]["rank_walls_ms"],
+                  "note": "world_size / backend as the process group reports them (nccl = RCCL); each rank's "
+                          "median region wall, before the max over ranks"},
+        "timing": {"regions": R, "region_walls_ms": res[args.mode]["region_walls_ms"],
+                   "note": "each region times exactly `steps` steps between barrier + synchronize pairs "
+                           "(host wall clock, max over ranks); value = the median region"},
+    }
+    if not args.full:
+        # the plain run ends here: set-up, warm-up, the timed steps, the line
+        sim.close()
+        if grouped:
+            barrier()
+            dist.destroy_process_group()
+        if rank == 0:
+            print(json.dumps(out))
+        return
     # fused mode: the other trajectory layout over the same action rows, timed the same way and
     # reported beside (it continues the same handle's arenas)
     other_layout = None
@@ -736,8 +873,9 @@ def main():
 
     # P1/P2 actions handed over from host memory (FS_ACT_HOST: pinned staging + H2D copy per
     # step), the PCIe-inclusive rate of the per-step path; reported beside, never as `value`
-    kh = min(K, 500)
-    p1h, p2h = p1[W:W + kh].cpu().numpy(), p2[W:W + kh].cpu().numpy()
+    kh = min(K, 500, rows_total)
+    Wr = W if W + kh <= rows_total else 0  # (the legs that index the rows themselves stay inside the table)
+    p1h, p2h = p1[Wr:Wr + kh].cpu().numpy(), p2[Wr:Wr + kh].cpu().numpy()
 
     def run_host(k0, n):
         for k in range(n):
@@ -748,7 +886,7 @@ def main():
     # the per-step path with the multi-GPU exchange of SURVEY 8(e): every step's outputs written
     # as 40-B records by the step kernel itself (fs_step_rec; before r05: fs_step + a separate
     # fs_pack_outputs launch) and gathered over RCCL/xGMI
-    kg = min(K, 500)
+    kg = kh
     rec = torch.empty((N, _abi.FS_RECORD_BYTES), dtype=torch.uint8, device=dev)
     gbuf = torch.empty((world * N, _abi.FS_RECORD_BYTES), dtype=torch.uint8, device=dev)
     fs_step_rec = L.fs_step_rec
@@ -761,7 +899,7 @@ def main():
                 check(rc, h)
             if grouped and args.dist_backend == "nccl":
                 dist.all_gather_into_tensor(gbuf, rec)
-    gwall = leg_median(run_step_gather, W, kg)
+    gwall = leg_median(run_step_gather, Wr, kg)
 
     def run_step_gather_root(k0, n):  # the learner-only variant: grouped send / recv to rank 0
         from footsies_gym_amd.parallel import gather_records_to
@@ -771,7 +909,7 @@ def main():
                 check(rc, h)
             if grouped and args.dist_backend == "nccl":
                 gather_records_to(rec, 0)
-    grwall = leg_median(run_step_gather_root, W, kg)
+    grwall = leg_median(run_step_gather_root, Wr, kg)
     # The dominant kernel of the reported mode, back-to-back launches.  The roofline block is
     # measured at a fixed launch shape (--roofline-ticks ticks per fs_step_n launch, the shape
     # the committed rocprofv3 summaries under profiles/ cover), independent of --steps; the
@@ -809,36 +947,7 @@ def main():
     # kernel nearer that limit than HBM's (the C3 kernel: 0.90 of its issue plateau, ~0.3 of HBM)
     hbm_frac = achieved / HBM_PEAK_GBPS
     bound = "simd-issue" if issue and (issue.get("issue_frac") or 0.0) > hbm_frac else "hbm"
-    other = "step" if args.mode == "fused" else "fused"
-    out = {
-        "metric": METRIC,
-        "value": res[args.mode]["env_steps_per_s"],
-        "unit": "env-steps/s",
-        "n_gpus": world,
-        "steps": K,
-        "warmup": W,
-        "ms_per_step": res[args.mode]["ms_per_step"],
-        "higher_is_better": True,
-        "scaling": scaling,
-        "vs_baseline": None,
-        "dtype": "int32+f32 (reward f64)",
-        "data": "synthetic (splitmix64 self-play actions in HBM)",
-        "library": library_info(),
-        "config": {"workload": ("C4 strong: %d arenas over %d GPUs" % (N * world, world) if args.global_envs else
-                                "C3: %d arenas/GPU" % N) + ", self-play random actions, P2 external, auto-reset same-step",
-                   "envs_per_gpu": N, "global_envs": N * world, "mode": args.mode,
-                   "ticks_per_launch": chunk if args.mode == "fused" else 1,
-                   "trajectory": ("packed records (fs_step_n_packed)" if packed else "one array per field (fs_step_n)")
-                   if args.mode == "fused" else None, "parallelism": "arena-shard x%d" % world},
-        "ranks": {"world_size": dist.get_world_size() if grouped else 1,
-                  "backend": dist.get_backend() if grouped else None,
-                  "launcher": "WORLD_SIZE" in os.environ, "solo_group_error": solo_group_error,
-                  "rank_walls_ms": res[args.mode]["rank_walls_ms"],
-                  "note": "world_size / backend as the process group reports them (nccl = RCCL); each rank's "
-                          "median region wall, before the max over ranks"},
-        "timing": {"regions": R, "region_walls_ms": res[args.mode]["region_walls_ms"],
-                   "note": "each region times exactly `steps` steps between barrier + synchronize pairs "
-                           "(host wall clock, max over ranks); value = the median region"},
+    out.update({
         "roofline": {"bound": bound, "achieved": achieved, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
                      "frac": achieved / HBM_PEAK_GBPS, "traffic": tr[0] if tr else None,
                      "traffic_ratio": (tr[0] / bytes_per_launch) if tr else None,
@@ -877,7 +986,7 @@ def main():
                                   "bytes_into_rank0_per_step": (world - 1) * N * _abi.FS_RECORD_BYTES,
                                   "note": "fs_step_rec + the records of every rank gathered to rank 0 "
                                           "only (grouped send / recv over RCCL, parallel.gather_records_to)"},
-    }
+    })
     # BASELINE configs[3] (C4): 262 144 arenas split over the N ranks (strong scaling), so the
     # driver's plain `bench.py --gpus N` at N = 1, 2, 4, 8 records C4's scaling curve -- its N = 1
     # point is all 262 144 arenas on one GPU.  Each rank: a second handle over its contiguous global
@@ -890,9 +999,9 @@ def main():
         c4n, c4b = c4_split(world, rank)
         try:
             sim4 = FootsiesSim(c4n, device=local, p2_mode="external", seed=0, arena_base=c4b)
-            rows4 = max(W + R * K, (R + 1) * LEG_TICKS)
-            a41, a42 = sim4.hash_actions(rows4, seed=args.seed, t0=0)
             ch4 = chunk if args.mode == "fused" else 1
+            rows4 = max(ch4, LEG_TICKS, min(max(W + R * K, (R + 1) * LEG_TICKS), ACTION_BYTES // (2 * c4n)))
+            a41, a42 = sim4.hash_actions(rows4, seed=args.seed, t0=0)
             tr4 = sim4.alloc_packed_trajectory(max(ch4, LEG_TICKS))
             _, f4 = make_runs(a41, a42, tr4, ch4, packed=True, handle=sim4.handle, n=c4n)
             _, f4k = make_runs(a41, a42, tr4, LEG_TICKS, packed=True, handle=sim4.handle, n=c4n)

@@ -48,6 +48,68 @@ def test_c4_split():
     assert bench.c4_split(3, 0) is None  # no even split: the leg is skipped
 
 
+def test_dump_outputs_sample(tmp_path):
+    """--dump-outputs' writer on host arrays: the last tick of every arena and the sampled arenas
+    of every tick the last launch wrote (rows past `ticks` are stale and stay out), float32 with
+    reward in float64, final_* zeroed where the arena did not end, the same sample for the same
+    seed; and the step-mode form, one row per arena."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    rng = np.random.default_rng(3)
+    rows, ticks, n = 9, 7, 1000
+    f = {"guard": rng.integers(0, 4, (rows, n, 2)).astype(np.uint8), "frame": rng.integers(0, 5000, (rows, n)).astype(np.int32),
+         "reward": rng.standard_normal((rows, n)), "terminated": (rng.random((rows, n)) < 0.3).astype(np.uint8),
+         "truncated": (rng.random((rows, n)) < 0.1).astype(np.uint8),
+         "final_position": rng.standard_normal((rows, n, 2)).astype(np.float32),
+         "final_frame": rng.integers(1, 5000, (rows, n)).astype(np.int32)}
+    a, b = tmp_path / "a", tmp_path / "b"
+    bench.dump_outputs(str(a), f, ticks, 0x5EED)
+    bench.dump_outputs(str(b), f, ticks, 0x5EED)
+    assert sorted(os.listdir(a)) == sorted(os.listdir(b)) and len(os.listdir(a)) == 2 * len(f) + 2
+    for name in os.listdir(a):
+        assert np.load(a / name).tobytes() == np.load(b / name).tobytes(), name
+    idx = np.load(a / "traj_arena_index.npy").astype(np.int64)
+    assert len(idx) == bench.DUMP_ARENAS and np.all(np.diff(idx) > 0)
+    assert np.array_equal(np.load(a / "last_arena_index.npy"), np.arange(n))
+    ended = (f["terminated"] | f["truncated"]).astype(bool)[:ticks]
+    for name, v in f.items():
+        v = v[:ticks]
+        if name.startswith("final_"):
+            v = np.where(ended if v.ndim == 2 else ended[..., None], v, 0)
+        t, last = np.load(a / ("traj_%s.npy" % name)), np.load(a / ("last_%s.npy" % name))
+        assert t.dtype == last.dtype == (np.float64 if name == "reward" else np.float32)
+        assert np.array_equal(t, v[:, idx]) and np.array_equal(last, v[-1])
+    c = tmp_path / "c"
+    bench.dump_outputs(str(c), {k: v[2] for k, v in f.items()}, None, 1)
+    assert len(os.listdir(c)) == len(f) + 1
+    assert np.array_equal(np.load(c / "last_frame.npy"), f["frame"][2])
+    assert np.array_equal(np.load(c / "last_final_frame.npy"), np.where(ended[2], f["final_frame"][2], 0))
+
+
+@pytest.mark.parametrize("n, rows", [(65536, 1000), (65536, 4096), (262144, 1000)])
+def test_dump_outputs_stays_under_64_mb(tmp_path, n, rows):
+    """The dump of every output field (alloc_trajectory's names, dtypes and shapes) at the default
+    shape (65 536 arenas, 1000-tick launches), at a launch longer than DUMP_TICKS and at C4's
+    262 144 arenas: the files' bytes equal the count from DUMP_ARENAS / DUMP_TICKS /
+    DUMP_LAST_ARENAS and stay under 64 MB.  (Zero arrays broadcast to the full shapes: no memory.)"""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    from footsies_gym_amd import _abi
+    f = {name: np.broadcast_to(np.zeros((), dtype=dt), (rows, n, cols) if cols > 1 else (rows, n))
+         for name, (dt, cols) in _abi.OUTPUT_SPEC.items()}
+    bench.dump_outputs(str(tmp_path), f, rows, 0x5EED)
+    per = sum((8 if dt == "f8" else 4) * cols for dt, cols in _abi.OUTPUT_SPEC.values())  # bytes per arena and tick
+    kept = min(rows, bench.DUMP_TICKS) * min(n, bench.DUMP_ARENAS) + min(n, bench.DUMP_LAST_ARENAS)
+    index = 8 * (min(n, bench.DUMP_ARENAS) + min(n, bench.DUMP_LAST_ARENAS))
+    data = sum(np.load(tmp_path / name).nbytes for name in os.listdir(tmp_path))
+    assert data == per * kept + index
+    assert sum(os.path.getsize(tmp_path / name) for name in os.listdir(tmp_path)) < 64 * 10**6
+    assert np.load(tmp_path / "traj_position.npy").shape == (min(rows, bench.DUMP_TICKS), bench.DUMP_ARENAS, 2)
+    assert np.load(tmp_path / "last_reward.npy").shape == (min(n, bench.DUMP_LAST_ARENAS),)
+
+
 @pytest.mark.parametrize("gpus", [2, 3, 4])
 def test_gpus_n_launches_n_ranks(gpus):
     p = run_bench(["--gpus", str(gpus), "--dry-run", "--dist-backend", "gloo", "--steps", "20", "--regions", "3",

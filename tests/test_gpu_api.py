@@ -565,7 +565,7 @@ def test_bench_json_contract(extra):
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--envs", "4096", "--steps", "100", "--warmup", "10",
-           "--chunk", "50", "--no-extras", "--cpu-seconds", "0.5", "--kernel-samples", "10"] + extra
+           "--chunk", "50", "--full", "--no-extras", "--cpu-seconds", "0.5", "--kernel-samples", "10"] + extra
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=300, check=True).stdout
     lines = [l for l in out.splitlines() if l.startswith("{")]
     assert len(lines) == 1
@@ -597,7 +597,7 @@ def test_bench_extras_legs():
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--envs", "2048", "--steps", "20", "--warmup", "5",
-           "--chunk", "20", "--roofline-ticks", "20", "--no-cpu-baseline", "--kernel-samples", "5"]
+           "--chunk", "20", "--full", "--roofline-ticks", "20", "--no-cpu-baseline", "--kernel-samples", "5"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=110, check=True).stdout
     d = json.loads([l for l in out.splitlines() if l.startswith("{")][-1])
     # (the side legs use the headline's trajectory layout, packed by default)
@@ -612,6 +612,62 @@ def test_bench_extras_legs():
     assert d["fused_other_layout"]["value"] > 0
     v = d["vector_env"]["numpy"]
     assert v["steps"] >= 200 and v["warmup_steps"] >= 200 and v["terminals_per_step"] > 0
+
+
+def test_bench_plain_run_and_dump_outputs(tmp_path):
+    """A plain bench run (no --full) prints the headline fields alone, times exactly --steps steps
+    in one region, and --dump-outputs writes the last launch's trajectory: equal to the same
+    launches made here (warm-up of 5, then 20 + 10 ticks: the last launch is a partial one), the
+    sampled arenas for every tick and every arena for the last tick, float32 / float64."""
+    import json
+    import os
+    import subprocess
+    import sys
+    import torch
+    from footsies_gym_amd.simulator import FootsiesSim, unpack_trajectory
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    n, seed = 300, 0x5EED
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--envs", str(n), "--steps", "30",
+           "--warmup", "5", "--chunk", "20", "--dump-outputs", str(tmp_path)]
+    out = subprocess.run(cmd, capture_output=True, text=True, timeout=110, check=True).stdout
+    lines = [l for l in out.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "n_gpus", "steps", "warmup"):
+        assert k in d, k
+    assert d["steps"] == 30 and d["timing"]["regions"] == 1 and len(d["timing"]["region_walls_ms"]) == 1
+    # (the listed wall is rounded to 1e-4 ms, of a region of some 0.05 ms)
+    assert d["ms_per_step"] == pytest.approx(d["timing"]["region_walls_ms"][0] / 30, rel=1e-2)
+    assert d["value"] == pytest.approx(n * 1e3 / d["ms_per_step"], rel=1e-9)
+    for k in ("roofline", "cpu_baseline", "step_gather_mode", "c4_strong", "step_mode", "vector_env"):
+        assert k not in d, k
+    sim = FootsiesSim(n, p2_mode="external", seed=0, arena_base=0)
+    p1, p2 = sim.hash_actions(35, seed=seed, t0=0)
+    traj = sim.alloc_packed_trajectory(20)
+    for k0, m in ((0, 5), (5, 20), (25, 10)):
+        sim.step_n_packed(m, p1[k0:k0 + m], p2[k0:k0 + m], trajectory=traj)
+    torch.cuda.synchronize()
+    want = {k: v[:10].cpu().numpy() for k, v in unpack_trajectory(traj).items()}
+    sim.close()
+    idx = np.load(tmp_path / "traj_arena_index.npy").astype(np.int64)
+    assert len(idx) == 256 and np.all(np.diff(idx) > 0) and idx[-1] < n
+    assert np.array_equal(np.load(tmp_path / "last_arena_index.npy"), np.arange(n))
+    ended = (want["terminated"] | want["truncated"]).astype(bool)
+    total = 0
+    for name, w in want.items():
+        if name.startswith("final_"):
+            w = np.where(ended if w.ndim == 2 else ended[..., None], w, 0)
+        got_t, got_l = np.load(tmp_path / ("traj_%s.npy" % name)), np.load(tmp_path / ("last_%s.npy" % name))
+        assert got_t.dtype == got_l.dtype == (np.float64 if name == "reward" else np.float32), name
+        assert np.array_equal(got_t, w[:, idx].astype(got_t.dtype)), name
+        assert np.array_equal(got_l, w[-1].astype(got_l.dtype)), name
+        total += got_t.nbytes + got_l.nbytes
+    # (the 64 MB bound at the default shape: tests/test_bench_launch.py::test_dump_outputs_stays_under_64_mb)
+    assert len(os.listdir(tmp_path)) == 2 * len(want) + 2 and total == 120 * (10 * 256 + n)
+    c = d["config"]  # 5 warm-up rows + 30 timed ones, all resident: none read twice
+    assert c["action_rows"] == c["action_rows_needed"] == 35 and c["action_rows_repeat"] is False
+    assert "read again" not in d["data"]
+    assert np.any(want["frame"] != 0) and np.any(want["position"] != 0)
 
 
 def test_native_consumer_under_host_sanitizers():

@@ -2,7 +2,7 @@
 
 The driver's scaling runs use RCCL with one GPU per rank; this box has one GPU, so these tests
 run the same calls at world size 1, where RCCL still runs its own kernels and copies:
-* `bench.py --gpus 1` under `torch.distributed.run` (a launcher, so bench joins a process group):
+* `bench.py --gpus 1 --full` under `torch.distributed.run` (a launcher, so bench joins a process group):
   barrier, the max-over-ranks all_reduce, the per-step all_gather of packed records and the
   grouped send / recv path, with the line reporting backend "nccl" and world size 1;
 * `ShardedSim.gather()` (all_gather_into_tensor) and `gather(dst=0)` over RCCL return exactly the
@@ -31,7 +31,7 @@ def free_port():
 def test_bench_under_launcher_runs_rccl_at_world_one():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=1",
            "--master-addr=127.0.0.1", "--master-port=%d" % free_port(), os.path.join(ROOT, "bench.py"),
-           "--gpus", "1", "--steps", "20", "--warmup", "5", "--envs", "4096", "--roofline-ticks", "20",
+           "--gpus", "1", "--full", "--steps", "20", "--warmup", "5", "--envs", "4096", "--roofline-ticks", "20",
            "--kernel-samples", "5", "--no-cpu-baseline", "--no-extras"]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     out = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=110)
@@ -44,9 +44,9 @@ def test_bench_under_launcher_runs_rccl_at_world_one():
 
 
 def test_plain_one_gpu_bench_gathers_over_rccl():
-    """The driver's plain `bench.py --gpus 1` (no launcher) forms a one-rank RCCL group, so its per-step
+    """`bench.py --gpus 1 --full` without a launcher forms a one-rank RCCL group, so its per-step
     gather leg runs the all_gather (VERDICT r05 weak #6); --no-solo-group keeps the old ungrouped run."""
-    args = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5",
+    args = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--full", "--steps", "20", "--warmup", "5",
             "--envs", "4096", "--roofline-ticks", "20", "--kernel-samples", "5", "--no-cpu-baseline", "--no-extras",
             "--no-c4"]
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}

@@ -10,7 +10,7 @@ mkdir -p "$OUT"
 cd /tmp; export TMPDIR=/tmp
 run() { name=$1; shift
   timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$ROOT/$OUT/$name" -o run "$@" \
-    -- python3 "$ROOT/bench.py" $ARGS > "$ROOT/$OUT/$name.log" 2>&1
+    -- python3 "$ROOT/bench.py" --full $ARGS > "$ROOT/$OUT/$name.log" 2>&1
 }
 run trace
 run fetch --pmc FETCH_SIZE

@@ -7,7 +7,7 @@
 #     -> gpurun_out/pmc_TAG.
 # Then, back in the build container, reduce them to the committed files:
 #   python3 tools/summarize_profile.py gpurun_out/prof_TAG TAG --envs 65536 --chunk 1000 \
-#       --command "python3 bench.py --no-cpu-baseline --no-extras --no-c4 --warmup 1000"
+#       --command "python3 bench.py --full --no-cpu-baseline --no-extras --no-c4 --warmup 1000"
 #   python3 tools/summarize_profile.py gpurun_out/pmc_TAG_c4 TAG_c4 --envs 262144 --chunk 1000 \
 #       --command "python3 tools/profile_driver.py --mode fused --envs 262144 --chunk 1000 --launches 3 --layout packed"
 #   python3 tools/pmc_table.py gpurun_out/pmc_TAG --ticks 1000 --waves 2048 --kernel k_step_n_packed \

@@ -40,7 +40,7 @@ def main():
     ap.add_argument("tag")
     ap.add_argument("--envs", type=int, default=65536)
     ap.add_argument("--chunk", type=int, default=100)
-    ap.add_argument("--command", default="python3 bench.py --steps 400 --warmup 100 --no-cpu-baseline")
+    ap.add_argument("--command", default="python3 bench.py --full --steps 400 --warmup 100 --no-cpu-baseline")
     a = ap.parse_args()
     out = os.path.join(ROOT, "profiles")
     os.makedirs(out, exist_ok=True)
