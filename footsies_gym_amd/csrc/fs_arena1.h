@@ -91,7 +91,7 @@ struct Arena1 {
   uint32_t bin;           // P2 bot's input (TrainingBattleAIActor.input), bot handles
   uint32_t pending, has_term;
   double cum;
-  AInfo ai0, ai1;         // ActionInfo of each fighter's action (re-read at the end of every tick)
+  uint32_t te0, te1;      // each fighter's tick entry (tick_entry; re-read after every collision)
   Bot1 bot;               // FS_P2_BOT only
 };
 
@@ -307,13 +307,25 @@ __device__ __forceinline__ void write_packed1(const Arena1& A, uint4* base, uint
   st_off(reinterpret_cast<PkRec*>(base), 32u * r + 16u, packed_record1(A.f1, A.rec_count, A.rec1, w3_p2));
 }
 
+// next_tick_entry for both fighters of the arena, one wave-uniform test for the pair (the branch
+// first: the one-lane kernel runs at two or more waves per SIMD)
+__device__ __forceinline__ void next_tick_entries1(Arena1& A) {
+  if (__builtin_expect(__builtin_amdgcn_ballot_w64((uint32_t)(A.f0.frame | A.f1.frame) >= (uint32_t)kTickFrames) != 0, 0)) {
+    A.te0 = tick_entry_slow(A.f0);
+    A.te1 = tick_entry_slow(A.f1);
+  } else {
+    A.te0 = tick_entry(A.f0);
+    A.te1 = tick_entry(A.f1);
+  }
+}
+
 // (see opaque_burst_results)
 __device__ __forceinline__ void opaque_burst_results1(Arena1& A) {
   asm volatile("" : "+v"(A.f0.x), "+v"(A.f0.act), "+v"(A.f0.frame), "+v"(A.f0.vital), "+v"(A.f0.guard),
                "+v"(A.f0.hits), "+v"(A.f0.buf), "+v"(A.f0.rsv), "+v"(A.f0.hold), "+v"(A.f0.won), "+v"(A.f0.hist));
   asm volatile("" : "+v"(A.f1.x), "+v"(A.f1.act), "+v"(A.f1.frame), "+v"(A.f1.vital), "+v"(A.f1.guard),
                "+v"(A.f1.hits), "+v"(A.f1.buf), "+v"(A.f1.rsv), "+v"(A.f1.hold), "+v"(A.f1.won), "+v"(A.f1.hist));
-  asm volatile("" : "+v"(A.ai0), "+v"(A.ai1), "+v"(A.cum), "+v"(A.pending), "+v"(A.has_term), "+v"(A.frame_count),
+  asm volatile("" : "+v"(A.te0), "+v"(A.te1), "+v"(A.cum), "+v"(A.pending), "+v"(A.has_term), "+v"(A.frame_count),
                "+v"(A.rec_count));
 }
 
@@ -339,7 +351,8 @@ __device__ __forceinline__ void env_step1(Arena1& A, uint32_t a1, uint32_t a2, c
     A.pending = 0;
     A.has_term = 0;
     A.cum = 0.0;
-    A.ai0 = A.ai1 = stand_info();
+    A.te0 = tick_entry_after_burst(A.f0);
+    A.te1 = tick_entry_after_burst(A.f1);
     settle2<WAIT>(n1, n2);
     if constexpr (PK) {
       write_packed1(A, o.pk_lanes, r, 0u);
@@ -369,16 +382,14 @@ __device__ __forceinline__ void env_step1(Arena1& A, uint32_t a1, uint32_t a2, c
   }
   const InputEval e0 = update_input(A.f0, in0, kRelLut0);
   const InputEval e1 = update_input(A.f1, in1, kRelLut1);
-  const AInfo ai0 = A.ai0, ai1 = A.ai1;
-  increment_action_frame(A.f0, ai0);
-  increment_action_frame(A.f1, ai1);
-  // both fighters' request entries and continuing records in flight together: the selects are
+  int rc0, rc1;  // the new frames, the continuing records and the request classes, from the entries
+  const uint32_t cls0 = tick_begin(A.f0, A.te0, &rc0), cls1 = tick_begin(A.f1, A.te1, &rc1);
+  // both fighters' request entries in flight together: the selects are
   // made opaque so that neither chain is sunk into a branch (which would serialize the reads)
   bool keep0, keep1;
-  uint32_t sel0 = request_sel(A.f0, e0, ai0, keep0), sel1 = request_sel(A.f1, e1, ai1, keep1);
+  uint32_t sel0 = request_sel_cls(A.f0, e0, cls0, keep0), sel1 = request_sel_cls(A.f1, e1, cls1, keep1);
   asm volatile("" : "+v"(sel0), "+v"(sel1));
   const uint32_t q0 = sT.req_table[sel0], q1 = sT.req_table[sel1];
-  const int rc0 = frame_record<false>(A.f0), rc1 = frame_record<false>(A.f1);
   uint32_t rs0, rs1;
   const bool set0 = apply_request(A.f0, q0, keep0, e0, &rs0);
   const bool set1 = apply_request(A.f1, q1, keep1, e1, &rs1);
@@ -404,8 +415,7 @@ __device__ __forceinline__ void env_step1(Arena1& A, uint32_t a1, uint32_t a2, c
   asm volatile("" ::"v"(R0.push), "v"(R0.hurt), "v"(R0.hit), "v"(R1.push), "v"(R1.hurt), "v"(R1.hit), "v"(resA),
                "v"(resB), "v"(ymA), "v"(ymB));
   hitbox_hurtbox_collision1<FM>(A.f0, A.f1, R0, R1, resA, resB, ymA, ymB);
-  A.ai0 = action_info<false>(A.f0.act);  // the next tick's ActionInfo, read early
-  A.ai1 = action_info<false>(A.f1.act);
+  next_tick_entries1(A);  // the next tick's entries, read early
   // KO check (BC:212-213) and reward (FE:382-405): per fighter, bit 0 = vital 0, bit 1 = guard dropped
   const uint32_t fl1 = ((uint32_t)(A.f0.vital - 1) >> 31) | (((uint32_t)(A.f0.guard - gb0) >> 31) << 1);
   const uint32_t fl2 = ((uint32_t)(A.f1.vital - 1) >> 31) | (((uint32_t)(A.f1.guard - gb1) >> 31) << 1);
@@ -432,7 +442,8 @@ __device__ __forceinline__ void env_step1(Arena1& A, uint32_t a1, uint32_t a2, c
       reset_burst1<FM, P2>(A, true);
       A.cum = 0.0;
       A.has_term = 0;
-      A.ai0 = A.ai1 = stand_info();
+      A.te0 = tick_entry_after_burst(A.f0);
+      A.te1 = tick_entry_after_burst(A.f1);
     } else {
       A.pending = 1;
       A.has_term = 1;
@@ -451,7 +462,7 @@ __device__ __forceinline__ void env_step1(Arena1& A, uint32_t a1, uint32_t a2, c
     st_off(o.terminated, r, (uint8_t)(over ? 1 : 0));
     st_off(o.truncated, r, (uint8_t)0);
   }
-  asm volatile("" ::"v"(A.ai0), "v"(A.ai1));
+  asm volatile("" ::"v"(A.te0), "v"(A.te1));
 }
 
 // The fused rollout, one lane per arena.  Both action rows of tick t + D are issued at the top of
@@ -497,8 +508,7 @@ __device__ __forceinline__ void step_body1(const StepParams& p) {
     for (int j = 0; j < D; j++) asm volatile("s_waitcnt vmcnt(0)" ::"v"(fl1[j]), "v"(fl2[j]) : "memory");
     return;
   }
-  A.ai0 = action_info<false>(A.f0.act);
-  A.ai1 = action_info<false>(A.f1.act);
+  next_tick_entries1(A);
   const uint32_t row_step = (uint32_t)p.out_stride_steps * N;
   uint32_t rd1, rd2;  // the rows of the current tick, resident
   asm volatile("s_waitcnt vmcnt(0)\n\tv_mov_b32 %0, %2\n\tv_mov_b32 %1, %3" : "=v"(rd1), "=v"(rd2)

@@ -7,15 +7,19 @@
 //
 //   load (coalesced 4/8/16-B per lane) -> n ticks in registers -> store
 //
-// Frame data is one 31 KB image (fs_tables.h), staged into LDS per block by the fused launches
+// Frame data is one 35 KB image (fs_tables.h), staged into LDS per block by the fused launches
 // and read in place from global memory by the one-tick launch: per action a 16-B ActionInfo
 // (frame count, loop, cancel window), per (action, frame) an index into 53 de-duplicated frame
 // records (three 16-B entries of x geometry and velocity) -- the window scans of
 // ActionData.cs:87-168 resolved offline (tools/gen_tables.py) -- the request chain's outcome per
 // (action, window state, inputs), the box-pair y overlaps per record pair and the hit resolution
-// per (attacker hit count, attacker record).  A tick's dependent LDS round trips: action info
-// (issued after the previous tick's collision), then the record index and the request-table
-// entry together, then the frame record with the y-overlap bits and the resolution entry.  The
+// per (attacker hit count, attacker record) -- and, for the fused launches, one 16-bit tick entry
+// per (action, in hitstun?, frame): the next tick's frame, its frame record and its request class
+// (IncrementActionFrame and the cancel-window tests resolved offline too).  A fused tick's
+// dependent LDS round trips: the tick entry (issued after the previous tick's collision), then
+// the request-table entry, then the frame record with the y-overlap bits and the resolution
+// entry; the one-tick launch carries ActionInfo instead and reads the record index with the
+// request-table entry.  The
 // 180-deep input histories
 // (Fighter.cs:98-101) are two 16-frame shift registers (backward / forward relative to the
 // fighter's facing) plus a saturating attack-hold counter: the reference
@@ -44,9 +48,9 @@ constexpr int NONE = 31;  // empty buffer / reserve slot
 constexpr uint32_t IN_LEFT = 1, IN_RIGHT = 2, IN_ATTACK = 4;
 
 // ---------------------------------------------------------------------------
-// frame data staged in LDS.  Every lookup of the tick (action info -> record index and
-// request entry -> frame record) is a dependent, lane-divergent load; from LDS it costs
-// ~tens of cycles instead of an L1/L2 round trip.  31 KB per block, copied once per fused
+// frame data staged in LDS.  Every lookup of the tick (tick entry -> request entry -> frame
+// record) is a dependent, lane-divergent load; from LDS it costs
+// ~tens of cycles instead of an L1/L2 round trip.  35 KB per block, copied once per fused
 // launch by all threads of the block.
 // ---------------------------------------------------------------------------
 __shared__ Tables sT;
@@ -339,7 +343,8 @@ __device__ __forceinline__ void increment_action_frame(Fighter& f, AInfo ai) {
 // SetCurrentAction ran; then *rec is the new action's frame-0 record.
 // The request table entry a fighter reads this tick (`keep`: hasWon or an early return, which
 // leave the guard latches alone) ...
-__device__ __forceinline__ uint32_t request_sel(const Fighter& f, const InputEval& e, AInfo ai, bool& keep) {
+// (`cls`: 2 = the action has ended, 1 = it sits in its cancel window, else 0)
+__device__ __forceinline__ uint32_t request_sel_cls(const Fighter& f, const InputEval& e, uint32_t cls, bool& keep) {
   // (take_rsv = rsv set & no stun; take_buf = !take_rsv & buf set & (hit or whiff-cancel) & no stun,
   // as bitwise ops: the short-circuit form materializes each condition as a 0 / 1 word)
   const int rsv = f.rsv, buf = f.buf;
@@ -347,15 +352,21 @@ __device__ __forceinline__ uint32_t request_sel(const Fighter& f, const InputEva
   const bool won = f.won != 0;
   const bool early = (f.stun <= 0) & (has_rsv | ((buf != NONE) & (kCanCancelOnWhiff | (f.hits > 0))));
   const int a0 = has_rsv ? rsv : buf;
-  const bool ended = f.frame >= ai_frame_count(ai);
-  const bool inwin = (f.frame >= ai_cancel_lo(ai)) & (f.frame <= ai_cancel_hi(ai));
-  const uint32_t cls = ended ? 2u : (inwin ? 1u : 0u);
   // (the low five bits XOR-swizzled with the action, as tools/gen_tables.py lays the table out:
   // lanes that differ in action but not in inputs read different LDS banks)
   const uint32_t in8 = ((9u * cls + 3u * e.atk + e.dash) << 3) | (e.held << 1) | (uint32_t)f.prox;
   const uint32_t idx = ((uint32_t)f.act << 8) | (in8 ^ (uint32_t)f.act);
   keep = early | won;
   return won ? (uint32_t)kReqWin + 3u * (uint32_t)f.act + cls : (early ? (uint32_t)(kReqEarly + a0) : idx);
+}
+// (the one-tick launch: the class from the ActionInfo it carries)
+__device__ __forceinline__ uint32_t request_cls(const Fighter& f, AInfo ai) {
+  const bool ended = f.frame >= ai_frame_count(ai);
+  const bool inwin = (f.frame >= ai_cancel_lo(ai)) & (f.frame <= ai_cancel_hi(ai));
+  return ended ? 2u : (inwin ? 1u : 0u);
+}
+__device__ __forceinline__ uint32_t request_sel(const Fighter& f, const InputEval& e, AInfo ai, bool& keep) {
+  return request_sel_cls(f, e, request_cls(f, ai), keep);
 }
 // ... and what the entry q does to it.  Returns whether SetCurrentAction ran; then *rec is the new
 // action's frame-0 record.
@@ -421,6 +432,65 @@ __device__ __forceinline__ RecGeo frame_rec(uint32_t k, uint32_t rec) {
 template <bool G>
 __device__ __forceinline__ int frame_record(const Fighter& f) {
   return tabs<G>().rec_index[f.act * kFrameStride + min(f.frame, kFrameStride - 1)];
+}
+
+// The tick entry (fs_tables.h Tables::tick), carried by the fused kernels in place of ActionInfo:
+// IncrementActionFrame's frame, the continuing frame record and the request class of the next
+// tick are a function of (action, frame, in hitstun?), all three final once the collision has
+// run, so one 16-bit LDS read there replaces increment_action_frame, frame_record and request_cls
+// (and the rec_index read on the request chain) at the head of the next tick.
+//   [0,6) frame record | [6,8) request class | [8,..) the frame after the increment
+static_assert(kTickFrames == 64 && sizeof(Tables::tick[0][0]) == 128 && sizeof(Tables::tick[0]) == 256,
+              "tick_entry's byte offset: (act << 8) | (stunned << 7) | (frame << 1)");
+__device__ __forceinline__ uint32_t tick_entry(const Fighter& f) {  // f.frame < kTickFrames
+  // (the flag as min(stun, 1), opaque: written in C++ it becomes a compare and a select of 0 / 128,
+  // two instructions and a literal more than v_min_u32 and the shift folded into v_lshl_or_b32)
+  uint32_t stunned;
+  asm("v_min_u32_e32 %0, 1, %1" : "=v"(stunned) : "v"(f.stun));
+  const uint32_t off = (stunned << 7) | (((uint32_t)f.act << 8) | ((uint32_t)f.frame << 1));
+  return *reinterpret_cast<const uint16_t*>(reinterpret_cast<const char*>(&sT.tick[0][0][0]) + off);
+}
+// (after a reset burst: STAND at frame 0 or 1, hitstun surviving -- SetupBattleStart keeps it)
+__device__ __forceinline__ uint32_t tick_entry_after_burst(const Fighter& f) { return tick_entry(f); }
+// The same word for any frame, from ActionInfo and rec_index (the arithmetic k_step runs every
+// tick; tools/gen_tables.py proves the two equal): the frame field is as wide as the frame.
+__device__ __forceinline__ uint32_t tick_entry_slow(const Fighter& f) {
+  const AInfo ai = action_info<false>(f.act);
+  Fighter g = f;
+  increment_action_frame(g, ai);
+  return (uint32_t)frame_record<false>(g) | (request_cls(g, ai) << 6) | ((uint32_t)g.frame << 8);
+}
+// The entry the next tick starts from.  The table holds frames below kTickFrames; a wave with a
+// fighter past them (DEAD on its way to frame 500, a loaded state) takes the slow form on all its
+// lanes: a wave-uniform branch, never taken in a rollout from reset states.
+// READ_FIRST: the table read is issued ahead of the branch, at an in-bounds index (the frame's low
+// bits: one more VALU instruction), and the rare branch replaces its result.  A/B at 1000-tick
+// packed launches (profiles/r07a_ab_branch_shape.txt): with one wave per SIMD (the _pf kernels at
+// 32 768 arenas) the lone wave otherwise stalls on the branch before it can issue the read
+// (+1.5 % against the parent with the read first, -1.1 % with the branch first); with two waves
+// the partner fills that stall and the extra instruction is what costs (65 536 arenas: +1.1 %
+// against +1.8 %).
+template <bool READ_FIRST>
+__device__ __forceinline__ uint32_t next_tick_entry(const Fighter& f) {
+  const bool past = __builtin_amdgcn_ballot_w64(f.frame >= kTickFrames) != 0;
+  if constexpr (READ_FIRST) {
+    Fighter g = f;
+    g.frame &= kTickFrames - 1;
+    uint32_t te = tick_entry(g);
+    if (__builtin_expect(past, 0)) te = tick_entry_slow(f);
+    return te;
+  } else {
+    if (__builtin_expect(past, 0)) return tick_entry_slow(f);
+    return tick_entry(f);
+  }
+}
+// The head of a tick from its entry: IncrementActionFrame (F:140-166).  Returns the request class
+// of the new frame; *rec_cont is its frame record.
+__device__ __forceinline__ uint32_t tick_begin(Fighter& f, uint32_t te, int* rec_cont) {
+  f.stun -= f.stun > 0 ? 1 : 0;
+  f.frame = (int)(te >> 8);
+  *rec_cont = (int)(te & 63u);
+  return (te >> 6) & 3u;
 }
 
 // UpdateBoxes (F:671-697): world x of every box of the record, `R` being the record in
@@ -686,6 +756,9 @@ static_assert(move_plan_len(MP_FAR1) <= 8 * 16 && attack_plan_len(AP_DELAY_SPECI
               "plans fit eight code words");
 __constant__ const BotTables kBot = make_bot_tables();
 __shared__ BotTables sBot;
+// four blocks per CU must fit the 160 KB of LDS: the packed launch of 262 144 arenas runs at four
+// waves per SIMD
+static_assert(sizeof(Tables) + sizeof(BotTables) <= 40 * 1024, "the staged tables: at most 40 KB per block");
 template <bool G>
 __device__ __forceinline__ const BotTables& bots() {
   if constexpr (G) return kBot;
@@ -694,7 +767,7 @@ __device__ __forceinline__ const BotTables& bots() {
 
 // Copy the kTables image (fs_tables.h) and, for kernels with a scripted bot (BOTS), the bot
 // tables into LDS by LDS-DMA (global_load_lds_dwordx4: L2 -> LDS with no VGPR round trip, 1 KB
-// per wave instruction, 8 per wave for the 31 KB image).  The DMA lands at a wave-uniform LDS
+// per wave instruction, 9 per wave for the 35 KB image).  The DMA lands at a wave-uniform LDS
 // base + lane x 16, so each wave instruction fills one contiguous 1 KB piece of the image.
 // All threads of the block must call this before any early return.
 typedef __attribute__((address_space(1))) void* GlobalPtr;
@@ -922,7 +995,8 @@ struct Lane {
   uint32_t act;       // this player's remote actor's input (TrainingRemoteActor.input)
   uint32_t bin;       // this player's bot actor's input (TrainingBattleAIActor.input), bot lanes only
   uint32_t p2bot;     // kActors: P2's actor is the bot (replica)
-  AInfo ai;           // ActionInfo of f.act (reloaded at the end of every tick)
+  AInfo ai;           // k_step only: ActionInfo of f.act
+  uint32_t te;        // the fused kernels: the tick entry of (f.act, f.frame, f.stun > 0), re-read after every collision
   Bot bot;            // FS_P2_BOT only: this lane's queue + replicas (see Bot)
   FullBot fb;         // kActors only: this fighter's whole BattleAI
   uint4 rng;          // kActors only: the game's RNG (replica)
@@ -1424,16 +1498,18 @@ __device__ __forceinline__ void prio_slice(uint32_t grp) {
                ".Lprio_lo%=:\n\ts_setprio 0\n.Lprio_end%=:" :: "s"(now), "n"(kPrioSliceShift) : "scc");
 }
 
-// The burst leaves mostly constants in the lane (SetupBattleStart, STAND's ActionInfo).  Where
+// The burst leaves mostly constants in the lane (SetupBattleStart; k_step: STAND's ActionInfo).  Where
 // the pending branch joins the tick, the compiler would materialize those constants in the join
 // block under the full exec mask -- a dozen moves on every tick of every wave, pending or not.
 // Made opaque here, they are produced inside the branch, in the registers the tick's own results
 // occupy.
+template <bool G>
 __device__ __forceinline__ void opaque_burst_results(Lane& L) {
   asm volatile("" : "+v"(L.f.x), "+v"(L.f.act), "+v"(L.f.frame), "+v"(L.f.vital), "+v"(L.f.guard), "+v"(L.f.hits),
                "+v"(L.f.buf), "+v"(L.f.rsv), "+v"(L.f.hold), "+v"(L.f.won), "+v"(L.f.hist));
-  asm volatile("" : "+v"(L.ai), "+v"(L.cum), "+v"(L.pending), "+v"(L.has_term), "+v"(L.frame_count),
-               "+v"(L.rec_count));
+  if constexpr (G) asm volatile("" : "+v"(L.ai));
+  else asm volatile("" : "+v"(L.te));
+  asm volatile("" : "+v"(L.cum), "+v"(L.pending), "+v"(L.has_term), "+v"(L.frame_count), "+v"(L.rec_count));
 }
 
 // Tick t + 1's request inputs, prepared at the end of tick t (the fused row loop at one wave per
@@ -1459,10 +1535,9 @@ __device__ __forceinline__ uint32_t tick_input(const Lane& L, uint32_t a_own) {
 }
 __device__ __forceinline__ void prepare_request(Lane& L, uint32_t in, Pre& pre) {
   pre.e = update_input(L.f, in, L.k ? kRelLut1 : kRelLut0);
-  increment_action_frame(L.f, L.ai);
-  pre.rec_cont = frame_record<false>(L.f);
+  const uint32_t cls = tick_begin(L.f, L.te, &pre.rec_cont);
   bool keep;
-  const uint32_t sel = request_sel(L.f, pre.e, L.ai, keep);
+  const uint32_t sel = request_sel_cls(L.f, pre.e, cls, keep);
   pre.keep = keep;
   pre.q = sT.req_table[sel];
 }
@@ -1472,7 +1547,7 @@ __device__ __forceinline__ void env_step(Lane& L, uint32_t a_own, const StepPara
                                          const Pre& pre = Pre{}, bool use_pre = false) {
   constexpr bool BOT = P2 == FS_P2_BOT;
   constexpr bool G = TP == kTabGlobal;  // the tables from global memory: a one-tick launch (k_step),
-                                        // where no next tick reads L.ai
+                                        // which carries ActionInfo (L.ai) and no tick entry
   const DevOutputs& o = p.out;
   const uint32_t k = L.k;
   const Actors ac{p.p1_bot != 0, p.p2_resets != 0, p.p2_noop != 0};
@@ -1485,7 +1560,8 @@ __device__ __forceinline__ void env_step(Lane& L, uint32_t a_own, const StepPara
     L.pending = false;
     L.has_term = false;
     L.cum = 0.0;
-    L.ai = stand_info();  // the burst ends on STAND
+    if constexpr (G) L.ai = stand_info();  // the burst ends on STAND
+    else L.te = tick_entry_after_burst(L.f);
     settle_w<WAIT>(next);
     if constexpr (PK) {
       write_packed(L, o.pk_lanes, r, k == 0 ? (uint32_t)L.frame_count : 0u);
@@ -1499,7 +1575,7 @@ __device__ __forceinline__ void env_step(Lane& L, uint32_t a_own, const StepPara
         if (p.rec) write_record(L, p.rec, r, 0u, 0.0);
       }
     }
-    opaque_burst_results(L);
+    opaque_burst_results<G>(L);
     return;
   }
   // the actor inputs of this frame (TrainingManager.p1Input/p2Input, BC:383-447): a remote
@@ -1534,12 +1610,21 @@ __device__ __forceinline__ void env_step(Lane& L, uint32_t a_own, const StepPara
     set = apply_request(L.f, pre.q, pre.keep != 0, e, &rec_set);
   } else {
     e = update_input(L.f, in, face ? kRelLut1 : kRelLut0);
-    const AInfo ai = L.ai;  // ActionInfo of f.act, re-read at the end of the previous tick
-    increment_action_frame(L.f, ai);
-    // the record if the action continues, read alongside the request entry; a
-    // request that sets an action returns that action's frame-0 record
-    rec_cont = frame_record<G>(L.f);
-    set = update_action_request<G>(L.f, e, ai, &rec_set);
+    if constexpr (G) {
+      const AInfo ai = L.ai;  // ActionInfo of f.act (step_one)
+      increment_action_frame(L.f, ai);
+      // the record if the action continues, read alongside the request entry; a
+      // request that sets an action returns that action's frame-0 record
+      rec_cont = frame_record<G>(L.f);
+      set = update_action_request<G>(L.f, e, ai, &rec_set);
+    } else {
+      // the new frame, the record if the action continues and the request class, from the entry
+      // read after the previous tick's collision
+      const uint32_t cls = tick_begin(L.f, L.te, &rec_cont);
+      bool keep;
+      const uint32_t sel = request_sel_cls(L.f, e, cls, keep);
+      set = apply_request(L.f, sT.req_table[sel], keep, e, &rec_set);
+    }
   }
   L.f.rec = set ? (int)rec_set : rec_cont;
   // One LDS round trip for everything the rest of the tick reads from the tables: my frame
@@ -1578,9 +1663,9 @@ __device__ __forceinline__ void env_step(Lane& L, uint32_t a_own, const StepPara
            (ov(L.f.uy0, uymax0, o_hy1, hymax1) << 2) | (ov(L.f.uy1, uymax1, o_hy1, hymax1) << 3);
   }
   hitbox_hurtbox_collision<FM>(L.f, k, R.hurt, o_hw0, o_hw1, res, ym_t);
-  // the next tick's ActionInfo, issued now so its LDS latency hides behind the KO test, the
-  // reward and the stores (only the same-step reset below changes the action again: to STAND)
-  if constexpr (!G) L.ai = action_info<G>(L.f.act);
+  // the next tick's entry, issued now so its LDS latency hides behind the KO test, the reward
+  // and the stores (only the same-step reset below changes the fighter again, and re-reads it)
+  if constexpr (!G) L.te = next_tick_entry<PF>(L.f);
   // KO check (BC:212-213) and reward (FE:382-405), evaluated identically on both lanes: each
   // lane's flags (bit 0: vital 0, bit 1: guard dropped this tick; both fields are 0..3) cross
   // the pair once, then fl1 / fl2 are P1's / P2's
@@ -1617,7 +1702,8 @@ __device__ __forceinline__ void env_step(Lane& L, uint32_t a_own, const StepPara
       }
       L.cum = 0.0;
       L.has_term = false;
-      L.ai = stand_info();  // the burst ends on STAND
+      if constexpr (G) L.ai = stand_info();  // the burst ends on STAND
+      else L.te = tick_entry_after_burst(L.f);
     } else {
       L.pending = true;
       L.has_term = true;
@@ -1647,8 +1733,8 @@ __device__ __forceinline__ void env_step(Lane& L, uint32_t a_own, const StepPara
       if (p.rec) write_record(L, p.rec, r, over ? 1u : 0u, reward);
     }
   }
-  // all four words live until here (the tick reads three; see R.push above)
-  if constexpr (!G) asm volatile("" ::"v"(L.ai));
+  // live until here (see R.push above)
+  if constexpr (!G) asm volatile("" ::"v"(L.te));
 }
 
 // P1's observation features for the in-kernel actor (fs_policy.h), packed bf16x2:
@@ -1718,7 +1804,7 @@ __device__ __forceinline__ void step_body(const StepParams& p) {
   } else {
     if (!active) return;
   }
-  L.ai = action_info<false>(L.f.act);
+  L.te = next_tick_entry<false>(L.f);
   if constexpr (POL) {
     const uint32_t row_step = (uint32_t)p.out_stride_steps * (uint32_t)p.n_envs;
     const uint32_t arena0 = (uint32_t)(l & ~63) >> 1;

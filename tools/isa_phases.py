@@ -61,6 +61,12 @@ PHASES = {
     "opaque_burst_results": "KO -> End -> Intro -> Fight burst (BC:212-345) [rare]",
     "stand_info": "KO -> End -> Intro -> Fight burst (BC:212-345) [rare]",
     "action_info": "next tick's ActionInfo read (F:140-166 / 472-510 inputs)",
+    "tick_begin": "IncrementActionFrame (F:140-166)",
+    "request_sel_cls": "UpdateActionRequest: request-table index (F:201-286)",
+    "next_tick_entry": "next tick's entry read: frame, record, request class (F:140-166, AD:87-168)",
+    "tick_entry": "next tick's entry read: frame, record, request class (F:140-166, AD:87-168)",
+    "tick_entry_after_burst": "KO -> End -> Intro -> Fight burst (BC:212-345) [rare]",
+    "tick_entry_slow": "next tick's entry from ActionInfo, frames past the table [rare]",
     "settle_w": "action rows: wait for the next tick's row (TrainingRemoteActor input)",
     "row_load": "action rows: load (TrainingRemoteActor input)",
     "prio_slice": "wave priority slice (scheduling, no C# counterpart)",
@@ -86,7 +92,7 @@ ENV_STEP_MARKS = [
 ]
 RARE_TAG = "[rare]"
 # functions charged wherever they sit in the chain (the rare work nested inside a common phase)
-NESTED = {"notify_damaged", "attack_info"}
+NESTED = {"notify_damaged", "attack_info", "tick_entry_slow", "tick_entry_after_burst"}
 # small helpers that belong to their caller's phase: charged to the call site's line in env_step
 HELPERS = {"xpair", "xp1", "xp2", "fadd", "fsub", "fadd2", "fsub2", "tabs", "bit0_mask", "splat", "sel4",
            "ai_frame_count", "ai_loop_from", "ai_cancel_lo", "ai_cancel_hi"}

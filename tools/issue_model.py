@@ -74,6 +74,10 @@ def main_loop(insts):
                 loops.append((addr[tgt], i))
     # the general-geometry loop reads kRecY (global_load_dwordx4); the standard tick has no 16-byte
     # global loads (its tables are in LDS, its row loads single bytes)
+    # (a backward branch that spans the barrier of the table staging or the kernel's end is no tick
+    # loop: the return from a cold block laid out behind the kernel, such as tick_entry_slow's)
+    loops = [lp for lp in loops
+             if not any(insts[j][1] in ("s_barrier", "s_endpgm") for j in range(lp[0], lp[1] + 1))] or loops
     std = [lp for lp in loops if not any(insts[j][1] == "global_load_dwordx4" for j in range(lp[0], lp[1] + 1))]
     pool = std or loops
     return max(pool, key=lambda lp: lp[1] - lp[0]) if pool else None
