@@ -1498,18 +1498,32 @@ __device__ __forceinline__ void prio_slice(uint32_t grp) {
                ".Lprio_lo%=:\n\ts_setprio 0\n.Lprio_end%=:" :: "s"(now), "n"(kPrioSliceShift) : "scc");
 }
 
+// Launch modes of the fused row loop (env_step's and row_loop's LM).  What a launch fixes for all of
+// its ticks -- the auto-reset mode, the reward kind, the priority slicing -- and whether any lane of
+// the wave starts with a reset pending are tested once per wave, before the loop (step_body), and
+// the common case runs a loop compiled for it: same-step auto-reset, dense reward, no lane of the
+// wave pending.  Same-step never sets `pending`, so that loop has no pending path and carries
+// neither `pending` nor `has_term` (0 after every same-step tick: set once behind the loop), and
+// none of the tests of StepParams::dense_reward / autoreset_mode / prio.  Everything else -- next-step
+// mode, sparse reward, a wave that loaded a pending lane -- takes the generic loop.
+constexpr int kLmGeneric = 0;   // every test at run time
+constexpr int kLmFast = 1;      // the common case, no priority slices (one wave per SIMD)
+constexpr int kLmFastPrio = 2;  // the common case with priority slices
+
 // The burst leaves mostly constants in the lane (SetupBattleStart; k_step: STAND's ActionInfo).  Where
 // the pending branch joins the tick, the compiler would materialize those constants in the join
 // block under the full exec mask -- a dozen moves on every tick of every wave, pending or not.
 // Made opaque here, they are produced inside the branch, in the registers the tick's own results
-// occupy.
-template <bool G>
+// occupy.  (FLAGS: the lane's pending / has_term too; the specialised loops do not carry them.)
+template <bool G, bool FLAGS = true>
 __device__ __forceinline__ void opaque_burst_results(Lane& L) {
   asm volatile("" : "+v"(L.f.x), "+v"(L.f.act), "+v"(L.f.frame), "+v"(L.f.vital), "+v"(L.f.guard), "+v"(L.f.hits),
                "+v"(L.f.buf), "+v"(L.f.rsv), "+v"(L.f.hold), "+v"(L.f.won), "+v"(L.f.hist));
   if constexpr (G) asm volatile("" : "+v"(L.ai));
   else asm volatile("" : "+v"(L.te));
-  asm volatile("" : "+v"(L.cum), "+v"(L.pending), "+v"(L.has_term), "+v"(L.frame_count), "+v"(L.rec_count));
+  if constexpr (FLAGS)
+    asm volatile("" : "+v"(L.cum), "+v"(L.pending), "+v"(L.has_term), "+v"(L.frame_count), "+v"(L.rec_count));
+  else asm volatile("" : "+v"(L.cum), "+v"(L.frame_count), "+v"(L.rec_count));
 }
 
 // Tick t + 1's request inputs, prepared at the end of tick t (the fused row loop at one wave per
@@ -1542,7 +1556,8 @@ __device__ __forceinline__ void prepare_request(Lane& L, uint32_t in, Pre& pre) 
   pre.q = sT.req_table[sel];
 }
 
-template <int FM, int P2, int WAIT = -1, int TP = kTabLds, bool GEOM = false, bool PK = false, bool PF = false>
+template <int FM, int P2, int WAIT = -1, int TP = kTabLds, bool GEOM = false, bool PK = false, bool PF = false,
+          int LM = kLmGeneric>
 __device__ __forceinline__ void env_step(Lane& L, uint32_t a_own, const StepParams& p, uint32_t r, uint32_t& next,
                                          const Pre& pre = Pre{}, bool use_pre = false) {
   constexpr bool BOT = P2 == FS_P2_BOT;
@@ -1551,7 +1566,8 @@ __device__ __forceinline__ void env_step(Lane& L, uint32_t a_own, const StepPara
   const DevOutputs& o = p.out;
   const uint32_t k = L.k;
   const Actors ac{p.p1_bot != 0, p.p2_resets != 0, p.p2_noop != 0};
-  if (L.pending) {  // FS_AUTORESET_NEXT_STEP: this step runs the reset burst only
+  constexpr bool FAST = LM != kLmGeneric;  // (no pending lane, same-step reset, dense reward: see kLmFast)
+  if (!FAST && L.pending) {  // FS_AUTORESET_NEXT_STEP: this step runs the reset burst only
     reset_burst<FM, P2, G>(L, true, ac);
     if constexpr (GEOM) {  // the round start's position (x, 0) and facing (F:123-124)
       L.f.y = 0.0f;
@@ -1594,7 +1610,11 @@ __device__ __forceinline__ void env_step(Lane& L, uint32_t a_own, const StepPara
   BotPre bpre;
   if constexpr (BOT) bpre = bot_prefetch<G>(L.bot, k);  // consumed by this tick's bot call, at its end
   L.frame_count++;
-  if (L.rec_count < kMaxRecording) {  // RecordInput (BC:593-607)
+  if constexpr (FAST) {  // RecordInput (BC:593-607) as two selects: no exec mask of its own
+    const bool recs = L.rec_count < kMaxRecording;
+    L.rec = recs ? in : L.rec;
+    L.rec_count += recs ? 1u : 0u;
+  } else if (L.rec_count < kMaxRecording) {  // RecordInput (BC:593-607)
     L.rec = in;
     L.rec_count++;
   }
@@ -1674,7 +1694,7 @@ __device__ __forceinline__ void env_step(Lane& L, uint32_t a_own, const StepPara
   const uint32_t any_fl = my_fl | o_fl;
   const bool over = (any_fl & 1u) != 0;
   double reward = 0.0;
-  if (p.dense_reward) {
+  if (FAST || p.dense_reward) {
     // Only a guard drop or the round's end moves the f64 sums: on other ticks the reward is
     // 0.0 and `cum += 0.0` is exact (cum starts at +0.0 and a sum of nonzero terms is never -0.0).
     if (any_fl != 0) {
@@ -1692,7 +1712,7 @@ __device__ __forceinline__ void env_step(Lane& L, uint32_t a_own, const StepPara
   if (over) {
     L.f.hist = 0;  // ChangeRoundState(KO): ClearInput (BC:296-299)
     L.f.hold = 0;
-    if (p.autoreset_mode == FS_AUTORESET_SAME_STEP) {
+    if (FAST || p.autoreset_mode == FS_AUTORESET_SAME_STEP) {
       if constexpr (PK) write_packed(L, o.pk_final, r, k == 0 ? (uint32_t)L.frame_count : 0u);
       else write_final(L, o, r);
       reset_burst<FM, P2, G>(L, true, ac);
@@ -1701,9 +1721,12 @@ __device__ __forceinline__ void env_step(Lane& L, uint32_t a_own, const StepPara
         L.f.flip = 0;
       }
       L.cum = 0.0;
-      L.has_term = false;
+      if constexpr (!FAST) L.has_term = false;
       if constexpr (G) L.ai = stand_info();  // the burst ends on STAND
       else L.te = tick_entry_after_burst(L.f);
+      // (without the pending path around the tick, this branch's join is where the burst's
+      // constants would be materialized on every tick: see opaque_burst_results)
+      if constexpr (FAST) opaque_burst_results<G, false>(L);
     } else {
       L.pending = true;
       L.has_term = true;
@@ -1719,7 +1742,7 @@ __device__ __forceinline__ void env_step(Lane& L, uint32_t a_own, const StepPara
       const uint32_t p1_act = xp1((uint32_t)L.f.act), p2_act = xp2((uint32_t)L.f.act);
       actors_request<G>(L, ac, bot_distance<FM>(x1, x2), p1_act, p2_act);
     }
-    L.has_term = false;
+    if constexpr (!FAST) L.has_term = false;
   }
   if constexpr (PK) {
     write_packed(L, o.pk_lanes, r, k == 0 ? (uint32_t)L.frame_count : (over ? 1u : 0u));
@@ -1746,6 +1769,65 @@ __device__ __forceinline__ void policy_features(const Lane& L, uint32_t& d0, uin
   const int mf = (a == A_STAND || a == A_FORWARD || a == A_BACKWARD) ? 0 : L.f.frame;
   d0 = pack_bf16x2((float)L.f.guard * (1.0f / 3.0f), (float)a * (1.0f / 16.0f));
   d1 = pack_bf16x2((float)mf * (1.0f / 55.0f), L.f.x * (1.0f / 4.6f));
+}
+
+// The fused launches' loop over action rows (step_body; `row0` / `row1`: rows 0 and 1, issued before
+// the table staging and resident), in launch mode LM.
+// Rows two ticks ahead, loaded and waited for as described at row_load, in two registers that swap
+// roles every tick (unrolled by two, so no register copy of a row in flight).  *_fl: a load in
+// flight (read only by its wait), *_rd: the row once resident.  A load is issued every tick (the
+// last rows re-read the last one) so the wait counts hold, and the last one in flight is waited
+// for before the wave ends.
+template <int FM, int P2, bool GEOM, bool PK, bool PF, int LM>
+__device__ __forceinline__ void row_loop(Lane& L, const StepParams& p, bool reads, const uint8_t* own, uint32_t row_mul,
+                                         int a, uint32_t row0, uint32_t row1) {
+  // (the wait count of settle_w: the vector memory ops every path issues between a row's load
+  // and its wait -- one tick's output stores, 10 per-field or 2 packed, plus the next row load)
+  constexpr int kRowWait = PK ? 3 : 11;
+  constexpr bool PRIO = LM == kLmFastPrio;
+  const int last = p.n_steps - 1;
+  const uint32_t row_step = (uint32_t)p.out_stride_steps * (uint32_t)p.n_envs;
+  uint32_t a_fl = row0, b_fl = row1, a_rd = row0, b_rd = row1;
+  const uint32_t grp = prio_group();
+  auto slice = [&] {
+    if constexpr (PRIO) prio_slice(grp);
+    else if constexpr (LM == kLmGeneric) {
+      if (p.prio) prio_slice(grp);
+    }
+  };
+  // PF: each tick but the launch's first starts from the request prepared at the end of the
+  // tick before it (prepare_request), from the row that tick made resident
+  Pre pre{};
+  bool have = false;
+  auto issue = [&](int t) -> uint32_t { return row_load(own + (uint32_t)min(t, last) * row_mul + (uint32_t)a); };
+  int t = 0;
+  for (; t < last; t += 2) {
+    a_fl = issue(t + 2);
+    slice();
+    env_step<FM, P2, kRowWait, kTabLds, GEOM, PK, PF, LM>(L, reads ? a_rd & 7u : 0u, p,
+                                                    (uint32_t)t * row_step + (uint32_t)a, b_fl, pre, have);
+    b_rd = b_fl;
+    if constexpr (PF) {
+      prepare_request(L, tick_input<P2>(L, reads ? b_rd & 7u : 0u), pre);
+      have = true;
+    }
+    b_fl = issue(t + 3);
+    slice();
+    env_step<FM, P2, kRowWait, kTabLds, GEOM, PK, PF, LM>(L, reads ? b_rd & 7u : 0u, p,
+                                                    (uint32_t)(t + 1) * row_step + (uint32_t)a, a_fl, pre, PF);
+    a_rd = a_fl;
+    if constexpr (PF) {
+      if (t + 2 <= last) prepare_request(L, tick_input<P2>(L, reads ? a_rd & 7u : 0u), pre);
+    }
+  }
+  if (t == last) {  // an odd tick count: the last tick waits for a re-read of the last row
+    a_fl = issue(t + 2);
+    uint32_t b_last = b_fl;  // (b_fl itself stays the in-flight value for the final wait)
+    env_step<FM, P2, kRowWait, kTabLds, GEOM, PK, PF, LM>(L, reads ? a_rd & 7u : 0u, p,
+                                                    (uint32_t)t * row_step + (uint32_t)a, b_last, pre, have);
+  }
+  asm volatile("s_waitcnt vmcnt(0)" ::"v"(a_fl), "v"(b_fl) : "memory");  // no load outlives the wave
+  if constexpr (LM != kLmGeneric) L.pending = L.has_term = 0;  // (what every same-step tick leaves; n_steps > 0)
 }
 
 // One fused launch over all arenas (k_step_n*, the rollout: state stays in registers between the
@@ -1839,50 +1921,26 @@ __device__ __forceinline__ void step_body(const StepParams& p) {
         env_step<FM, P2, -1, kTabLds, GEOM>(L, act & 7u, p, (uint32_t)t * row_step + (uint32_t)a, next);
       }
     } else {
-      // Rows two ticks ahead, loaded and waited for as described at row_load, in two registers
-      // that swap roles every tick (unrolled by two, so no register copy of a row in flight).
-      // *_fl: a load in flight (read only by its wait), *_rd: the row once resident.  A load is
-      // issued every tick (the last rows re-read the last one) so the wait counts hold, and the
-      // last one in flight is waited for before the wave ends.  (Rows 0 and 1 were issued before
-      // the table staging.)
-      // (the wait count of settle_w: the vector memory ops every path issues between a row's load
-      // and its wait -- one tick's output stores, 10 per-field or 2 packed, plus the next row load)
-      constexpr int kRowWait = PK ? 3 : 11;
-      uint32_t a_fl = next, b_fl = row1, a_rd, b_rd;
-      asm volatile("s_waitcnt vmcnt(0)\n\tv_mov_b32 %0, %2\n\tv_mov_b32 %1, %3" : "=v"(a_rd), "=v"(b_rd)
-                   : "v"(a_fl), "v"(b_fl) : "memory");
-      const uint32_t grp = prio_group();
-      // PF: each tick but the launch's first starts from the request prepared at the end of the
-      // tick before it (prepare_request), from the row that tick made resident
-      Pre pre{};
-      bool have = false;
-      int t = 0;
-      for (; t < last; t += 2) {
-        a_fl = issue(t + 2);
-        if (p.prio) prio_slice(grp);
-        env_step<FM, P2, kRowWait, kTabLds, GEOM, PK, PF>(L, reads ? a_rd & 7u : 0u, p,
-                                                        (uint32_t)t * row_step + (uint32_t)a, b_fl, pre, have);
-        b_rd = b_fl;
-        if constexpr (PF) {
-          prepare_request(L, tick_input<P2>(L, reads ? b_rd & 7u : 0u), pre);
-          have = true;
-        }
-        b_fl = issue(t + 3);
-        if (p.prio) prio_slice(grp);
-        env_step<FM, P2, kRowWait, kTabLds, GEOM, PK, PF>(L, reads ? b_rd & 7u : 0u, p,
-                                                        (uint32_t)(t + 1) * row_step + (uint32_t)a, a_fl, pre, PF);
-        a_rd = a_fl;
-        if constexpr (PF) {
-          if (t + 2 <= last) prepare_request(L, tick_input<P2>(L, reads ? a_rd & 7u : 0u), pre);
-        }
+      // the row loop, compiled once per launch mode (kLmFast); the choice is per wave -- no barrier
+      // follows the table staging, so the waves of a block may run different loops
+      // (rows 0 and 1 made resident here, ahead of the choice: no load is in flight where the loops
+      // part and meet)
+      uint32_t row0, row1_rd;  // (early-clobber outputs: the loads' registers die here)
+      asm volatile("s_waitcnt vmcnt(0)\n\tv_mov_b32 %0, %2\n\tv_mov_b32 %1, %3" : "=&v"(row0), "=&v"(row1_rd)
+                   : "v"(next), "v"(row1) : "memory");
+      const bool fast = p.autoreset_mode == FS_AUTORESET_SAME_STEP && p.dense_reward &&
+                        __builtin_amdgcn_ballot_w64(L.pending != 0) == 0;
+      // (the generic loop only: general geometry and the per-arena actors, off the throughput path,
+      // and the scripted bot, whose tick has no registers to spare for a second loop's allocation)
+      if constexpr (GEOM || P2 == kActors || P2 == FS_P2_BOT) {
+        row_loop<FM, P2, GEOM, PK, PF, kLmGeneric>(L, p, reads, own, row_mul, a, row0, row1_rd);
+      } else if constexpr (PF) {  // (one wave per SIMD: no slices unless forced)
+        if (fast && !p.prio) row_loop<FM, P2, GEOM, PK, PF, kLmFast>(L, p, reads, own, row_mul, a, row0, row1_rd);
+        else row_loop<FM, P2, GEOM, PK, PF, kLmGeneric>(L, p, reads, own, row_mul, a, row0, row1_rd);
+      } else {  // (without slices these launches are one-tick ones, or forced: the generic loop)
+        if (fast && p.prio) row_loop<FM, P2, GEOM, PK, PF, kLmFastPrio>(L, p, reads, own, row_mul, a, row0, row1_rd);
+        else row_loop<FM, P2, GEOM, PK, PF, kLmGeneric>(L, p, reads, own, row_mul, a, row0, row1_rd);
       }
-      if (t == last) {  // an odd tick count: the last tick waits for a re-read of the last row
-        a_fl = issue(t + 2);
-        uint32_t b_last = b_fl;  // (b_fl itself stays the in-flight value for the final wait)
-        env_step<FM, P2, kRowWait, kTabLds, GEOM, PK, PF>(L, reads ? a_rd & 7u : 0u, p,
-                                                        (uint32_t)t * row_step + (uint32_t)a, b_last, pre, have);
-      }
-      asm volatile("s_waitcnt vmcnt(0)" ::"v"(a_fl), "v"(b_fl) : "memory");  // no load outlives the wave
     }
   }
   if (active) {

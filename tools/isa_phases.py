@@ -8,7 +8,9 @@ fs_kernels.hip is compiled for gfx950 with the library's own flags (footsies_gym
 plus -gline-tables-only, which adds line tables with inlining records and leaves the code alone
 (checked here: the kernel's mnemonic sequence must equal the one in the built libfootsies.so).
 Every instruction of the main loop (the backward branch spanning the most instructions, two
-ticks of the row loop; tools/issue_model.main_loop) is symbolized with its full inline chain
+ticks of the row loop; tools/issue_model.main_loop -- or the row loop of a launch mode,
+fs_kernels.hip kLmFast, see mode_loop: by default the specialised loop where the kernel holds one,
+and the choice is printed) is symbolized with its full inline chain
 (llvm-symbolizer --inlines) and charged to the outermost function called from env_step (the
 tick), or to the env_step / step_body source line range it sits on when the tick body itself
 holds it.  Functions map to phases (PHASES below, with the C# each one restates).  Phases that
@@ -145,6 +147,34 @@ def line_marks(src_text):
     return sorted(out)
 
 
+def mode_loop(insts, mode):
+    """[start, end] of the standard row loop of one launch mode.  A kernel with a specialised loop
+    (fs_kernels.hip kLmFast / kLmFastPrio) holds two standard row loops, each two ticks with two
+    row loads (global_load_ubyte) and no 16-byte global load (the general-geometry loop reads kRecY
+    with them); the specialised one has no pending path and none of the launch-uniform tests, so it
+    is the shorter of the two."""
+    addr = {a: i for i, (a, *_rest) in enumerate(insts)}
+    loops = []
+    for i, (a, mn, ops, size) in enumerate(insts):
+        if mn.startswith("s_cbranch") or mn == "s_branch":
+            off = int(ops.split()[0])
+            off = off - 65536 if off >= 32768 else off
+            tgt = a + 4 + 4 * off
+            if off < 0 and tgt in addr:
+                body = [insts[j][1] for j in range(addr[tgt], i + 1)]
+                if "global_load_dwordx4" not in body and "s_barrier" not in body and "s_endpgm" not in body:
+                    loops.append((addr[tgt], i))
+    # (cold blocks laid out behind a loop return into it with backward branches of their own: the
+    # loop is the widest of those spans; the other mode's loop is the widest span apart from it)
+    loops.sort(key=lambda lp: lp[0] - lp[1])
+    first = loops[0]
+    rest = [lp for lp in loops if lp[1] < first[0] or lp[0] > first[1]]
+    assert rest, "expected a generic and a specialised row loop, found one"
+    loops = sorted([first, rest[0]], key=lambda lp: lp[1] - lp[0])
+    assert all([insts[j][1] for j in range(lo, hi + 1)].count("global_load_ubyte") == 2 for lo, hi in loops), loops
+    return loops[0] if mode == "fast" else loops[1]
+
+
 def kind(mn):
     if mn.startswith("v_mfma"):
         return "mfma"
@@ -172,6 +202,9 @@ def main():
     ap.add_argument("--lib", default=B.LIB)
     ap.add_argument("--sq", default=None, help="profiles/*_sq.json with the measured per-wave-tick counts")
     ap.add_argument("--json", default=None)
+    ap.add_argument("--loop", choices=["auto", "main", "fast", "generic"], default="auto",
+                    help="the row loop to attribute: the specialised one where the kernel has it, else the largest "
+                         "standard loop (auto); the largest standard loop (main); the one of a launch mode")
     a = ap.parse_args()
     src_text = open(a.src).read()
     with tempfile.TemporaryDirectory() as d:
@@ -183,7 +216,14 @@ def main():
             ship = IM.kernel_insts(IM.disassemble(a.lib), "<" + a.kernel + ">")
             same = [x[1] for x in ship] == [x[1] for x in insts]
             assert same, "the -gline-tables-only build differs from %s" % a.lib
-        lo, hi = IM.main_loop(insts)
+        if a.loop == "auto":  # the loop the common launch runs: the specialised one where there is one
+            try:
+                mode_loop(insts, "fast")
+                a.loop = "fast"
+            except AssertionError:
+                a.loop = "main"
+        lo, hi = IM.main_loop(insts) if a.loop == "main" else mode_loop(insts, a.loop)
+        print("loop: %s (%d instructions, two ticks)" % (a.loop, hi - lo + 1))
         loop = insts[lo:hi + 1]
         chains = symbolize(obj, [x[0] for x in loop])
     marks = line_marks(src_text)
@@ -205,10 +245,13 @@ def main():
                 if line >= first:
                     ph = p
             return ph
-        if "step_body" in names:
-            k = names.index("step_body")
-            if k + 1 < len(outer):
-                fn = outer[k + 1][0]
+        if "row_loop" in names or "step_body" in names:  # (the row loop is step_body's callee)
+            k = names.index("row_loop" if "row_loop" in names else "step_body")
+            k += 1
+            while k < len(outer) and outer[k][0] == "operator()":  # (row_loop's lambdas)
+                k += 1
+            if k < len(outer):
+                fn = outer[k][0]
                 return PHASES.get(fn, "loop: " + fn)
             return "loop control (step_body)"
         return "other: " + names[-1]
@@ -231,7 +274,7 @@ def main():
         rows.append(row)
         (rare if row["rare"] else common).update(c)
     rows.sort(key=lambda r: (r["rare"], -r["per_tick"].get("valu", 0), -r["total_per_tick"]))
-    res = {"kernel": a.kernel, "source": os.path.relpath(a.src, ROOT), "flags": "build.py flags_for(fs_kernels.hip) + -gline-tables-only "
+    res = {"kernel": a.kernel, "loop": a.loop, "source": os.path.relpath(a.src, ROOT), "flags": "build.py flags_for(fs_kernels.hip) + -gline-tables-only "
            "(same code as the library: mnemonic sequence checked)",
            "loop_instructions": len(loop), "ticks_in_loop": ticks,
            "common_path_per_tick": {k: v / ticks for k, v in sorted(common.items())},
