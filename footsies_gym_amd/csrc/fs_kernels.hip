@@ -344,6 +344,9 @@ __device__ __forceinline__ void increment_action_frame(Fighter& f, AInfo ai) {
 // The request table entry a fighter reads this tick (`keep`: hasWon or an early return, which
 // leave the guard latches alone) ...
 // (`cls`: 2 = the action has ended, 1 = it sits in its cancel window, else 0)
+// (INV: the lane is inside the fast loops' invariant set, see kLmFast -- hasWon is clear, so the
+// entry has no WIN case: no test of f.won, no divergent branch around the index arithmetic)
+template <bool INV = false>
 __device__ __forceinline__ uint32_t request_sel_cls(const Fighter& f, const InputEval& e, uint32_t cls, bool& keep) {
   // (take_rsv = rsv set & no stun; take_buf = !take_rsv & buf set & (hit or whiff-cancel) & no stun,
   // as bitwise ops: the short-circuit form materializes each condition as a 0 / 1 word)
@@ -356,6 +359,10 @@ __device__ __forceinline__ uint32_t request_sel_cls(const Fighter& f, const Inpu
   // lanes that differ in action but not in inputs read different LDS banks)
   const uint32_t in8 = ((9u * cls + 3u * e.atk + e.dash) << 3) | (e.held << 1) | (uint32_t)f.prox;
   const uint32_t idx = ((uint32_t)f.act << 8) | (in8 ^ (uint32_t)f.act);
+  if constexpr (INV) {
+    keep = early;
+    return early ? (uint32_t)(kReqEarly + a0) : idx;
+  }
   keep = early | won;
   return won ? (uint32_t)kReqWin + 3u * (uint32_t)f.act + cls : (early ? (uint32_t)(kReqEarly + a0) : idx);
 }
@@ -470,8 +477,11 @@ __device__ __forceinline__ uint32_t tick_entry_slow(const Fighter& f) {
 // (+1.5 % against the parent with the read first, -1.1 % with the branch first); with two waves
 // the partner fills that stall and the extra instruction is what costs (65 536 arenas: +1.1 %
 // against +1.8 %).
-template <bool READ_FIRST>
+// INV: every lane of the wave is inside the fast loops' invariant set (kLmFast), whose frames stay
+// below kTickFrames: the table read alone, no ballot and no branch.
+template <bool READ_FIRST, bool INV = false>
 __device__ __forceinline__ uint32_t next_tick_entry(const Fighter& f) {
+  if constexpr (INV) return tick_entry(f);
   const bool past = __builtin_amdgcn_ballot_w64(f.frame >= kTickFrames) != 0;
   if constexpr (READ_FIRST) {
     Fighter g = f;
@@ -1345,11 +1355,16 @@ __device__ __forceinline__ void st_off(T* base, uint32_t byte_off, T v) {
   __builtin_nontemporal_store(v, reinterpret_cast<T*>(reinterpret_cast<char*>(base) + byte_off));
 }
 
+// (REMAP = false: the fast loops' main record, written after the same-step burst -- the action is
+// never DEAD or WIN there, see kLmFast)
+template <bool REMAP = true>
 __device__ __forceinline__ void write_obs(const Lane& L, uint8_t* guard, uint8_t* move, float* move_frame,
                                           float* position, int32_t* frame, uint8_t* action, uint8_t* hitstun,
                                           uint32_t r) {
   int a = L.f.act;
-  if (a == A_DEAD || a == A_WIN) a = A_STAND;  // FE:537-549
+  if constexpr (REMAP) {
+    if (a == A_DEAD || a == A_WIN) a = A_STAND;  // FE:537-549
+  }
   const int mf = (a == A_STAND || a == A_FORWARD || a == A_BACKWARD) ? 0 : L.f.frame;  // FE:339-358
   const uint32_t c = 2 * r + L.k;
   st_off(guard, c, (uint8_t)L.f.guard);
@@ -1361,8 +1376,9 @@ __device__ __forceinline__ void write_obs(const Lane& L, uint8_t* guard, uint8_t
   st_off(frame, 4 * r, (int32_t)L.frame_count);  // both lanes hold the replica: the same value to the same address
 }
 
+template <bool REMAP = true>
 __device__ __forceinline__ void write_main(const Lane& L, const DevOutputs& o, uint32_t r) {
-  write_obs(L, o.guard, o.move, o.move_frame, o.position, o.frame, o.action, o.hitstun, r);
+  write_obs<REMAP>(L, o.guard, o.move, o.move_frame, o.position, o.frame, o.action, o.hitstun, r);
 }
 __device__ __forceinline__ void write_final(const Lane& L, const DevOutputs& o, uint32_t r) {
   write_obs(L, o.final_guard, o.final_move, o.final_move_frame, o.final_position, o.final_frame, o.final_action,
@@ -1374,9 +1390,12 @@ __device__ __forceinline__ void write_final(const Lane& L, const DevOutputs& o, 
 // word w3 (P1: the frame; P2: the terminated / truncated bytes) -- so that a tick's outputs take
 // two store instructions (this record and the f64 reward) instead of ten.
 typedef uint32_t PkRec __attribute__((ext_vector_type(4)));  // a native vector: one 16-B store
+template <bool REMAP = true>
 __device__ __forceinline__ PkRec packed_record(const Lane& L, uint32_t w3) {
   int a = L.f.act;
-  if (a == A_DEAD || a == A_WIN) a = A_STAND;  // FE:537-549
+  if constexpr (REMAP) {
+    if (a == A_DEAD || a == A_WIN) a = A_STAND;  // FE:537-549
+  }
   const int mf = (a == A_STAND || a == A_FORWARD || a == A_BACKWARD) ? 0 : L.f.frame;  // FE:339-358
   const uint32_t act = L.rec_count > 0 ? (uint32_t)L.rec : 0u;  // a 3-bit input
   PkRec v;
@@ -1389,8 +1408,9 @@ __device__ __forceinline__ PkRec packed_record(const Lane& L, uint32_t w3) {
   return v;
 }
 // lane record c = 2 r + k of row r (byte offset 16 c: the host keeps 32 r below 2^32)
+template <bool REMAP = true>
 __device__ __forceinline__ void write_packed(const Lane& L, uint4* base, uint32_t r, uint32_t w3) {
-  st_off(reinterpret_cast<PkRec*>(base), 16u * (2u * r + L.k), packed_record(L, w3));
+  st_off(reinterpret_cast<PkRec*>(base), 16u * (2u * r + L.k), packed_record<REMAP>(L, w3));
 }
 
 // fs_step_rec: arena r's FS_RECORD_BYTES gather record (fs_gather.hip k_pack_records' layout:
@@ -1506,9 +1526,28 @@ __device__ __forceinline__ void prio_slice(uint32_t grp) {
 // neither `pending` nor `has_term` (0 after every same-step tick: set once behind the loop), and
 // none of the tests of StepParams::dense_reward / autoreset_mode / prio.  Everything else -- next-step
 // mode, sparse reward, a wave that loaded a pending lane -- takes the generic loop.
+//
+// The specialised loops also settle, once per wave, three tests a rollout's lanes never pass: they
+// run only when every loaded lane of the wave is inside the set I (in_fast_set below) --
+//   hasWon clear | the action, the buffered and the reserved action none of DEAD / WIN |
+//   action frame < kTickFrames | vital <= 1
+// -- which one Fight tick with its same-step burst maps into itself for every input
+// (tools/gen_tables.py proves it from the frame data: prove_fast_loop_closure).  Inside I the request
+// has no hasWon case (request_sel_cls<true>), the next tick's entry is in the table
+// (next_tick_entry<.., true>), and the record written after the burst never shows DEAD or WIN: DEAD is
+// entered only by a hit that takes the last vital, which ends the round on that tick, and the burst
+// leaves STAND.  A lane outside I (a loaded state: a winner, a fighter on the ground, frame 64+, vital
+// 2-3) sends its wave to the generic loop.
 constexpr int kLmGeneric = 0;   // every test at run time
 constexpr int kLmFast = 1;      // the common case, no priority slices (one wave per SIMD)
 constexpr int kLmFastPrio = 2;  // the common case with priority slices
+// Is the fighter inside I?  (Tested once per launch, in step_body's prologue.)
+__device__ __forceinline__ bool in_fast_set(const Fighter& f) {
+  constexpr uint32_t kOut = (1u << A_DEAD) | (1u << A_WIN);  // (NONE = 31 is neither)
+  static_assert(A_DEAD < 31 && A_WIN < 31, "");
+  const uint32_t named = (1u << f.act) | (1u << f.buf) | (1u << f.rsv);
+  return (f.won == 0) & ((named & kOut) == 0) & (f.frame < kTickFrames) & (f.vital <= 1);
+}
 
 // The burst leaves mostly constants in the lane (SetupBattleStart; k_step: STAND's ActionInfo).  Where
 // the pending branch joins the tick, the compiler would materialize those constants in the join
@@ -1517,8 +1556,12 @@ constexpr int kLmFastPrio = 2;  // the common case with priority slices
 // occupy.  (FLAGS: the lane's pending / has_term too; the specialised loops do not carry them.)
 template <bool G, bool FLAGS = true>
 __device__ __forceinline__ void opaque_burst_results(Lane& L) {
-  asm volatile("" : "+v"(L.f.x), "+v"(L.f.act), "+v"(L.f.frame), "+v"(L.f.vital), "+v"(L.f.guard), "+v"(L.f.hits),
-               "+v"(L.f.buf), "+v"(L.f.rsv), "+v"(L.f.hold), "+v"(L.f.won), "+v"(L.f.hist));
+  if constexpr (FLAGS)
+    asm volatile("" : "+v"(L.f.x), "+v"(L.f.act), "+v"(L.f.frame), "+v"(L.f.vital), "+v"(L.f.guard), "+v"(L.f.hits),
+                 "+v"(L.f.buf), "+v"(L.f.rsv), "+v"(L.f.hold), "+v"(L.f.won), "+v"(L.f.hist));
+  else  // (the fast loops do not carry hasWon: 0 throughout, see in_fast_set)
+    asm volatile("" : "+v"(L.f.x), "+v"(L.f.act), "+v"(L.f.frame), "+v"(L.f.vital), "+v"(L.f.guard), "+v"(L.f.hits),
+                 "+v"(L.f.buf), "+v"(L.f.rsv), "+v"(L.f.hold), "+v"(L.f.hist));
   if constexpr (G) asm volatile("" : "+v"(L.ai));
   else asm volatile("" : "+v"(L.te));
   if constexpr (FLAGS)
@@ -1547,11 +1590,12 @@ __device__ __forceinline__ uint32_t tick_input(const Lane& L, uint32_t a_own) {
   if (L.k == 0 || P2 == FS_P2_EXTERNAL) return a_own;
   return P2 == FS_P2_BOT ? L.bin : 0u;
 }
+template <bool INV = false>
 __device__ __forceinline__ void prepare_request(Lane& L, uint32_t in, Pre& pre) {
   pre.e = update_input(L.f, in, L.k ? kRelLut1 : kRelLut0);
   const uint32_t cls = tick_begin(L.f, L.te, &pre.rec_cont);
   bool keep;
-  const uint32_t sel = request_sel_cls(L.f, pre.e, cls, keep);
+  const uint32_t sel = request_sel_cls<INV>(L.f, pre.e, cls, keep);
   pre.keep = keep;
   pre.q = sT.req_table[sel];
 }
@@ -1642,7 +1686,7 @@ __device__ __forceinline__ void env_step(Lane& L, uint32_t a_own, const StepPara
       // read after the previous tick's collision
       const uint32_t cls = tick_begin(L.f, L.te, &rec_cont);
       bool keep;
-      const uint32_t sel = request_sel_cls(L.f, e, cls, keep);
+      const uint32_t sel = request_sel_cls<FAST>(L.f, e, cls, keep);
       set = apply_request(L.f, sT.req_table[sel], keep, e, &rec_set);
     }
   }
@@ -1685,7 +1729,7 @@ __device__ __forceinline__ void env_step(Lane& L, uint32_t a_own, const StepPara
   hitbox_hurtbox_collision<FM>(L.f, k, R.hurt, o_hw0, o_hw1, res, ym_t);
   // the next tick's entry, issued now so its LDS latency hides behind the KO test, the reward
   // and the stores (only the same-step reset below changes the fighter again, and re-reads it)
-  if constexpr (!G) L.te = next_tick_entry<PF>(L.f);
+  if constexpr (!G) L.te = next_tick_entry<PF, FAST>(L.f);
   // KO check (BC:212-213) and reward (FE:382-405), evaluated identically on both lanes: each
   // lane's flags (bit 0: vital 0, bit 1: guard dropped this tick; both fields are 0..3) cross
   // the pair once, then fl1 / fl2 are P1's / P2's
@@ -1744,11 +1788,13 @@ __device__ __forceinline__ void env_step(Lane& L, uint32_t a_own, const StepPara
     }
     if constexpr (!FAST) L.has_term = false;
   }
+  // (the fast loops: this record follows the same-step burst, so no DEAD / WIN remap; pk_final /
+  // write_final in the KO branch above keep it)
   if constexpr (PK) {
-    write_packed(L, o.pk_lanes, r, k == 0 ? (uint32_t)L.frame_count : (over ? 1u : 0u));
+    write_packed<!FAST>(L, o.pk_lanes, r, k == 0 ? (uint32_t)L.frame_count : (over ? 1u : 0u));
     st_off(o.reward, 8 * r, reward);  // identical on both lanes of the arena
   } else {
-    write_main(L, o, r);
+    write_main<!FAST>(L, o, r);
     st_off(o.reward, 8 * r, reward);  // identical on both lanes of the arena
     st_off(o.terminated, r, (uint8_t)(over ? 1 : 0));
     st_off(o.truncated, r, (uint8_t)0);
@@ -1785,6 +1831,7 @@ __device__ __forceinline__ void row_loop(Lane& L, const StepParams& p, bool read
   // and its wait -- one tick's output stores, 10 per-field or 2 packed, plus the next row load)
   constexpr int kRowWait = PK ? 3 : 11;
   constexpr bool PRIO = LM == kLmFastPrio;
+  if constexpr (LM != kLmGeneric) L.f.won = 0;  // (inside I, and nothing in the tick sets it: not carried)
   const int last = p.n_steps - 1;
   const uint32_t row_step = (uint32_t)p.out_stride_steps * (uint32_t)p.n_envs;
   uint32_t a_fl = row0, b_fl = row1, a_rd = row0, b_rd = row1;
@@ -1808,7 +1855,7 @@ __device__ __forceinline__ void row_loop(Lane& L, const StepParams& p, bool read
                                                     (uint32_t)t * row_step + (uint32_t)a, b_fl, pre, have);
     b_rd = b_fl;
     if constexpr (PF) {
-      prepare_request(L, tick_input<P2>(L, reads ? b_rd & 7u : 0u), pre);
+      prepare_request<LM != kLmGeneric>(L, tick_input<P2>(L, reads ? b_rd & 7u : 0u), pre);
       have = true;
     }
     b_fl = issue(t + 3);
@@ -1817,7 +1864,7 @@ __device__ __forceinline__ void row_loop(Lane& L, const StepParams& p, bool read
                                                     (uint32_t)(t + 1) * row_step + (uint32_t)a, a_fl, pre, PF);
     a_rd = a_fl;
     if constexpr (PF) {
-      if (t + 2 <= last) prepare_request(L, tick_input<P2>(L, reads ? a_rd & 7u : 0u), pre);
+      if (t + 2 <= last) prepare_request<LM != kLmGeneric>(L, tick_input<P2>(L, reads ? a_rd & 7u : 0u), pre);
     }
   }
   if (t == last) {  // an odd tick count: the last tick waits for a re-read of the last row
@@ -1929,7 +1976,7 @@ __device__ __forceinline__ void step_body(const StepParams& p) {
       asm volatile("s_waitcnt vmcnt(0)\n\tv_mov_b32 %0, %2\n\tv_mov_b32 %1, %3" : "=&v"(row0), "=&v"(row1_rd)
                    : "v"(next), "v"(row1) : "memory");
       const bool fast = p.autoreset_mode == FS_AUTORESET_SAME_STEP && p.dense_reward &&
-                        __builtin_amdgcn_ballot_w64(L.pending != 0) == 0;
+                        __builtin_amdgcn_ballot_w64((L.pending != 0) | !in_fast_set(L.f)) == 0;
       // (the generic loop only: general geometry and the per-arena actors, off the throughput path,
       // and the scripted bot, whose tick has no registers to spare for a second loop's allocation)
       if constexpr (GEOM || P2 == kActors || P2 == FS_P2_BOT) {

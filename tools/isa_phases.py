@@ -91,6 +91,8 @@ ENV_STEP_MARKS = [
     ("TrainingManager.Step -> RequestNextInput", "BattleAI (AI:41-403)"),
     ("if constexpr (PK) {\n    write_packed(L, o.pk_lanes, r, k == 0 ? (uint32_t)L.frame_count : (over",
      "outputs: EnvironmentState / obs / info (BC:449-468, FE:336-380)"),
+    ("if constexpr (PK) {\n    write_packed<!FAST>(L, o.pk_lanes, r, k == 0 ? (uint32_t)L.frame_count : (over",
+     "outputs: EnvironmentState / obs / info (BC:449-468, FE:336-380)"),
 ]
 RARE_TAG = "[rare]"
 # functions charged wherever they sit in the chain (the rare work nested inside a common phase)
