@@ -1157,9 +1157,11 @@ __device__ __forceinline__ AttackInfo attack_info(int i) {
 
 // `res` = kTables.resolve[o_hits * kNumFrameRecs + o_rec], read with the frame record: byte m (the box-pair
 // overlap mask) holds the outcome at the attacker's hit count o_hits (low nibble) and at 0 (high).
+// The lookup, then what the outcome does (collision_lookup / collision_resolve: the specialised row
+// loops put a wave-wide gate between the two, see env_step).
 template <int FM>
-__device__ __forceinline__ void hitbox_hurtbox_collision(Fighter& f, uint32_t k, F4 my_hurt, float o_hw0, float o_hw1,
-                                                         U4 res, uint32_t ym) {
+__device__ __forceinline__ uint32_t collision_lookup(const Fighter& f, F4 my_hurt, float o_hw0, float o_hw1, U4 res,
+                                                     uint32_t ym) {
   // (no wave-level skip: absent hitboxes never overlap in y, ybits)
   const float o_hx0 = xpair(f.hx0), o_hx1 = xpair(f.hx1);
   const uint32_t xm = box_x_overlaps<FM>(o_hw0, o_hw1, o_hx0, o_hx1, my_hurt.zw, F2{f.ux0, f.ux1});
@@ -1171,7 +1173,10 @@ __device__ __forceinline__ void hitbox_hurtbox_collision(Fighter& f, uint32_t k,
   const uint32_t m = xm & ym;
   const uint32_t sel = (m & 7u) | 0x0c0c0c00u;
   const uint32_t lo = __builtin_amdgcn_perm(res.y, res.x, sel), hi = __builtin_amdgcn_perm(res.w, res.z, sel);
-  const uint32_t tab = (m & 8u) ? hi : lo;
+  return (m & 8u) ? hi : lo;
+}
+// `tab`: collision_lookup's byte.
+__device__ __forceinline__ void collision_resolve(Fighter& f, uint32_t k, uint32_t tab) {
   // On the P2 lane phase A's outcome (at P1's hit count); on the P1 lane phase B's, unless phase
   // A hit P2 -- which resets P2's hit count to 0 first (SetCurrentAction), so P1 then reads the
   // outcome at hit count 0.
@@ -1203,6 +1208,27 @@ __device__ __forceinline__ void hitbox_hurtbox_collision(Fighter& f, uint32_t k,
   const uint32_t mA = bit0_mask(pA), mB = bit0_mask(pB);
   const uint32_t sA = (mA & (pA >> 1)) | (~mA & (uint32_t)f.stun);
   f.stun = (int)((mB & (pB >> 1)) | (~mB & sA));
+}
+// The hit gate of the specialised row loops (kLmFast).  Everything collision_resolve does except
+// the proximity latch, and everything the tick does after it -- the KO test, the reward, the
+// same-step burst -- is a function of "some fighter was hit": with no lane of the wave hit, hitA,
+// pA and pB are 0 on every lane, so neither a hit count nor a hitstun changes; NotifyDamaged alone
+// writes vital and guard, and inside the set I (in_fast_set) every vital is 1, so no KO flag and no
+// guard drop: reward 0.0, `cum += 0.0` the identity, not over.  One wave-wide ballot of the lookup's
+// hit bit therefore sends the wave past all of it (about nine wave-ticks in ten of a rollout from
+// reset, tests/test_hit_gate_rollout.py).  The high nibble needs no test: it is read only where
+// phase A hit.  The ballot is wave-uniform, so behind it every pair exchange still runs with both
+// lanes of the pair enabled.
+__device__ __forceinline__ bool wave_has_hit(uint32_t tab) {
+  return __builtin_amdgcn_ballot_w64((tab & 1u) != 0) != 0;
+}
+// The no-hit path's whole effect: NotifyInProximityGuardRange (F:400-406), my_prox from the low nibble
+__device__ __forceinline__ void proximity_latch(Fighter& f, uint32_t tab) { f.prox |= (tab >> 3) & 1u & f.in_back; }
+
+template <int FM>
+__device__ __forceinline__ void hitbox_hurtbox_collision(Fighter& f, uint32_t k, F4 my_hurt, float o_hw0, float o_hw1,
+                                                         U4 res, uint32_t ym) {
+  collision_resolve(f, k, collision_lookup<FM>(f, my_hurt, o_hw0, o_hw1, res, ym));
 }
 
 // KO tick -> End (winner), End tick (BC:221-243, 306-325, 371-381), reduced to
@@ -1530,14 +1556,15 @@ __device__ __forceinline__ void prio_slice(uint32_t grp) {
 // The specialised loops also settle, once per wave, three tests a rollout's lanes never pass: they
 // run only when every loaded lane of the wave is inside the set I (in_fast_set below) --
 //   hasWon clear | the action, the buffered and the reserved action none of DEAD / WIN |
-//   action frame < kTickFrames | vital <= 1
+//   action frame < kTickFrames | vital == 1
 // -- which one Fight tick with its same-step burst maps into itself for every input
 // (tools/gen_tables.py proves it from the frame data: prove_fast_loop_closure).  Inside I the request
 // has no hasWon case (request_sel_cls<true>), the next tick's entry is in the table
 // (next_tick_entry<.., true>), and the record written after the burst never shows DEAD or WIN: DEAD is
 // entered only by a hit that takes the last vital, which ends the round on that tick, and the burst
-// leaves STAND.  A lane outside I (a loaded state: a winner, a fighter on the ground, frame 64+, vital
-// 2-3) sends its wave to the generic loop.
+// leaves STAND.  The vital term is what the loops' hit gate rests on (wave_has_hit).  A lane outside I
+// (a loaded state: a winner, a fighter on the ground, frame 64+, vital 0 or 2-3) sends its wave to the
+// generic loop.
 constexpr int kLmGeneric = 0;   // every test at run time
 constexpr int kLmFast = 1;      // the common case, no priority slices (one wave per SIMD)
 constexpr int kLmFastPrio = 2;  // the common case with priority slices
@@ -1546,7 +1573,7 @@ __device__ __forceinline__ bool in_fast_set(const Fighter& f) {
   constexpr uint32_t kOut = (1u << A_DEAD) | (1u << A_WIN);  // (NONE = 31 is neither)
   static_assert(A_DEAD < 31 && A_WIN < 31, "");
   const uint32_t named = (1u << f.act) | (1u << f.buf) | (1u << f.rsv);
-  return (f.won == 0) & ((named & kOut) == 0) & (f.frame < kTickFrames) & (f.vital <= 1);
+  return (f.won == 0) & ((named & kOut) == 0) & (f.frame < kTickFrames) & (f.vital == 1);
 }
 
 // The burst leaves mostly constants in the lane (SetupBattleStart; k_step: STAND's ActionInfo).  Where
@@ -1726,67 +1753,87 @@ __device__ __forceinline__ void env_step(Lane& L, uint32_t a_own, const StepPara
     ym_t = ov(L.f.uy0, uymax0, o_hy0, hymax0) | (ov(L.f.uy1, uymax1, o_hy0, hymax0) << 1) |
            (ov(L.f.uy0, uymax0, o_hy1, hymax1) << 2) | (ov(L.f.uy1, uymax1, o_hy1, hymax1) << 3);
   }
-  hitbox_hurtbox_collision<FM>(L.f, k, R.hurt, o_hw0, o_hw1, res, ym_t);
-  // the next tick's entry, issued now so its LDS latency hides behind the KO test, the reward
-  // and the stores (only the same-step reset below changes the fighter again, and re-reads it)
-  if constexpr (!G) L.te = next_tick_entry<PF, FAST>(L.f);
-  // KO check (BC:212-213) and reward (FE:382-405), evaluated identically on both lanes: each
-  // lane's flags (bit 0: vital 0, bit 1: guard dropped this tick; both fields are 0..3) cross
-  // the pair once, then fl1 / fl2 are P1's / P2's
-  const uint32_t my_fl = ((uint32_t)(L.f.vital - 1) >> 31) | (((uint32_t)(L.f.guard - guard_before) >> 31) << 1);
-  const uint32_t o_fl = xpair(my_fl);
-  const uint32_t any_fl = my_fl | o_fl;
-  const bool over = (any_fl & 1u) != 0;
-  double reward = 0.0;
-  if (FAST || p.dense_reward) {
-    // Only a guard drop or the round's end moves the f64 sums: on other ticks the reward is
-    // 0.0 and `cum += 0.0` is exact (cum starts at +0.0 and a sum of nonzero terms is never -0.0).
-    if (any_fl != 0) {
-      const uint32_t fl1 = k == 0 ? my_fl : o_fl, fl2 = k == 0 ? o_fl : my_fl;
-      if (fl1 & 2u) reward -= 0.3;
-      if (fl2 & 2u) reward += 0.3;
-      L.cum += reward;
-      if (over) reward += (double)((fl2 & 1u) ? 1 : -1) - L.cum;
-    }
-  } else {
-    const uint32_t fl2 = k == 0 ? o_fl : my_fl;
-    reward = over ? ((fl2 & 1u) ? 1.0 : -1.0) : 0.0;
+  // The specialised loops gate everything behind the collision's table lookup on whether any lane of
+  // the wave was hit (wave_has_hit): with none, the proximity latch and the next tick's entry are all
+  // that is left of the tick before its stores -- reward 0.0, not over.
+  const uint32_t tab = collision_lookup<FM>(L.f, R.hurt, o_hw0, o_hw1, res, ym_t);
+  bool wave_hit = true;
+  const uint32_t prox_before = L.f.prox;
+  if constexpr (FAST) {  // (the latch runs ahead of the gate and the hit path takes it back: no else side)
+    wave_hit = wave_has_hit(tab);
+    proximity_latch(L.f, tab);
+    asm volatile("" : "+v"(L.f.prox));
   }
-  settle_w<WAIT>(next);
-  if (over) {
-    L.f.hist = 0;  // ChangeRoundState(KO): ClearInput (BC:296-299)
-    L.f.hold = 0;
-    if (FAST || p.autoreset_mode == FS_AUTORESET_SAME_STEP) {
-      if constexpr (PK) write_packed(L, o.pk_final, r, k == 0 ? (uint32_t)L.frame_count : 0u);
-      else write_final(L, o, r);
-      reset_burst<FM, P2, G>(L, true, ac);
-      if constexpr (GEOM) {
-        L.f.y = 0.0f;
-        L.f.flip = 0;
+  if (__builtin_expect(wave_hit, !FAST)) {
+    if constexpr (FAST) L.f.prox = prox_before;
+    collision_resolve(L.f, k, tab);
+  }
+  // the next tick's entry, issued now so its LDS latency hides behind what is left of the tick: the
+  // KO test and the reward (the generic tick, and the specialised loops' hit path), the row wait and
+  // the record's pack and stores (only the same-step reset below changes the fighter again, and
+  // re-reads it)
+  if constexpr (!G) L.te = next_tick_entry<PF, FAST>(L.f);
+  if constexpr (FAST) settle_w<WAIT>(next);  // (ahead of the gated part: one wait statement for both paths)
+  bool over = false;
+  double reward = 0.0;
+  if (__builtin_expect(wave_hit, !FAST)) {
+    // KO check (BC:212-213) and reward (FE:382-405), evaluated identically on both lanes: each
+    // lane's flags (bit 0: vital 0, bit 1: guard dropped this tick; both fields are 0..3) cross
+    // the pair once, then fl1 / fl2 are P1's / P2's
+    const uint32_t my_fl = ((uint32_t)(L.f.vital - 1) >> 31) | (((uint32_t)(L.f.guard - guard_before) >> 31) << 1);
+    const uint32_t o_fl = xpair(my_fl);
+    const uint32_t any_fl = my_fl | o_fl;
+    over = (any_fl & 1u) != 0;
+    if (FAST || p.dense_reward) {
+      // Only a guard drop or the round's end moves the f64 sums: on other ticks the reward is
+      // 0.0 and `cum += 0.0` is exact (cum starts at +0.0 and a sum of nonzero terms is never -0.0).
+      if (any_fl != 0) {
+        const uint32_t fl1 = k == 0 ? my_fl : o_fl, fl2 = k == 0 ? o_fl : my_fl;
+        if (fl1 & 2u) reward -= 0.3;
+        if (fl2 & 2u) reward += 0.3;
+        L.cum += reward;
+        if (over) reward += (double)((fl2 & 1u) ? 1 : -1) - L.cum;
       }
-      L.cum = 0.0;
-      if constexpr (!FAST) L.has_term = false;
-      if constexpr (G) L.ai = stand_info();  // the burst ends on STAND
-      else L.te = tick_entry_after_burst(L.f);
-      // (without the pending path around the tick, this branch's join is where the burst's
-      // constants would be materialized on every tick: see opaque_burst_results)
-      if constexpr (FAST) opaque_burst_results<G, false>(L);
     } else {
-      L.pending = true;
-      L.has_term = true;
+      const uint32_t fl2 = k == 0 ? o_fl : my_fl;
+      reward = over ? ((fl2 & 1u) ? 1.0 : -1.0) : 0.0;
     }
-  } else {
-    if constexpr (BOT) {  // TrainingManager.Step -> RequestNextInput -> getNextAIInput
-      const float x1 = xp1(L.f.x), x2 = xp2(L.f.x);
-      const uint32_t p1_act = xp1((uint32_t)L.f.act);
-      const uint32_t bi = bot_next_input<G>(L.bot, k, bot_distance<FM>(x1, x2), p1_act, bpre);
-      L.bin = k == 1 ? bi : L.bin;
-    } else if constexpr (P2 == kActors) {  // the same, for the per-arena actors
-      const float x1 = xp1(L.f.x), x2 = xp2(L.f.x);
-      const uint32_t p1_act = xp1((uint32_t)L.f.act), p2_act = xp2((uint32_t)L.f.act);
-      actors_request<G>(L, ac, bot_distance<FM>(x1, x2), p1_act, p2_act);
+    if constexpr (!FAST) settle_w<WAIT>(next);
+    if (over) {
+      L.f.hist = 0;  // ChangeRoundState(KO): ClearInput (BC:296-299)
+      L.f.hold = 0;
+      if (FAST || p.autoreset_mode == FS_AUTORESET_SAME_STEP) {
+        if constexpr (PK) write_packed(L, o.pk_final, r, k == 0 ? (uint32_t)L.frame_count : 0u);
+        else write_final(L, o, r);
+        reset_burst<FM, P2, G>(L, true, ac);
+        if constexpr (GEOM) {
+          L.f.y = 0.0f;
+          L.f.flip = 0;
+        }
+        L.cum = 0.0;
+        if constexpr (!FAST) L.has_term = false;
+        if constexpr (G) L.ai = stand_info();  // the burst ends on STAND
+        else L.te = tick_entry_after_burst(L.f);
+        // (without the pending path around the tick, this branch's join is where the burst's
+        // constants would be materialized on every tick: see opaque_burst_results)
+        if constexpr (FAST) opaque_burst_results<G, false>(L);
+      } else {
+        L.pending = true;
+        L.has_term = true;
+      }
+    } else {
+      if constexpr (BOT) {  // TrainingManager.Step -> RequestNextInput -> getNextAIInput
+        const float x1 = xp1(L.f.x), x2 = xp2(L.f.x);
+        const uint32_t p1_act = xp1((uint32_t)L.f.act);
+        const uint32_t bi = bot_next_input<G>(L.bot, k, bot_distance<FM>(x1, x2), p1_act, bpre);
+        L.bin = k == 1 ? bi : L.bin;
+      } else if constexpr (P2 == kActors) {  // the same, for the per-arena actors
+        const float x1 = xp1(L.f.x), x2 = xp2(L.f.x);
+        const uint32_t p1_act = xp1((uint32_t)L.f.act), p2_act = xp2((uint32_t)L.f.act);
+        actors_request<G>(L, ac, bot_distance<FM>(x1, x2), p1_act, p2_act);
+      }
+      if constexpr (!FAST) L.has_term = false;
     }
-    if constexpr (!FAST) L.has_term = false;
   }
   // (the fast loops: this record follows the same-step burst, so no DEAD / WIN remap; pk_final /
   // write_final in the KO branch above keep it)

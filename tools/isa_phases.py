@@ -17,6 +17,14 @@ holds it.  Functions map to phases (PHASES below, with the C# each one restates)
 run only on rare lanes -- a landed hit (NotifyDamaged), the KO / reset burst, the terminal
 record -- are reported apart from the common path, whose per-tick counts are what
 profiles/*_sq.json measures (SQ_INSTS_VALU etc. per wave-tick).
+
+The specialised loops run the collision's resolution, the KO test and the reward only on wave-ticks
+with a hit (fs_kernels.hip wave_has_hit), and the compiler lays those blocks out behind the loop:
+the loop's own span is the no-hit path (about nine wave-ticks in ten of a rollout).  The blocks
+behind it that branch back into it are attributed too, their phases tagged [hit] (the rare ones
+among them -- NotifyDamaged, the burst -- stay [rare]), and the common path is reported twice: the
+no-hit path, and the hit path with the [hit] phases added.  In the generic loop, and in revisions
+without the gate, nothing is tagged and the two are the same.
 """
 import argparse
 import collections
@@ -50,6 +58,10 @@ PHASES = {
     "push_character_vs_background": "UpdatePushCharacterVsBackground (BC:503-519)",
     "apply_position_change": "ApplyPositionChange (F:331-350)",
     "hitbox_hurtbox_collision": "UpdateHitboxHurtboxCollision (BC:521-591)",
+    "collision_lookup": "UpdateHitboxHurtboxCollision (BC:521-591)",
+    "collision_resolve": "UpdateHitboxHurtboxCollision: resolution, NotifyAttackHit, SetHitStun (BC:535-591)",
+    "wave_has_hit": "hit gate: wave-wide ballot and branch (scheduling, no C# counterpart)",
+    "proximity_latch": "NotifyInProximityGuardRange (F:400-406)",
     "box_x_overlaps": "UpdateHitboxHurtboxCollision: BoxBase.Overlaps x (F:17-25)",
     "notify_damaged": "NotifyDamaged (F:357-398) [rare]",
     "attack_info": "NotifyDamaged: AttackData select [rare]",
@@ -95,6 +107,7 @@ ENV_STEP_MARKS = [
      "outputs: EnvironmentState / obs / info (BC:449-468, FE:336-380)"),
 ]
 RARE_TAG = "[rare]"
+HIT_TAG = " [hit]"  # appended in the specialised loops: runs only on wave-ticks with a hit
 # functions charged wherever they sit in the chain (the rare work nested inside a common phase)
 NESTED = {"notify_damaged", "attack_info", "tick_entry_slow", "tick_entry_after_burst"}
 # small helpers that belong to their caller's phase: charged to the call site's line in env_step
@@ -227,10 +240,26 @@ def main():
         lo, hi = IM.main_loop(insts) if a.loop == "main" else mode_loop(insts, a.loop)
         print("loop: %s (%d instructions, two ticks)" % (a.loop, hi - lo + 1))
         loop = insts[lo:hi + 1]
+        n_hot = len(loop)
+        if a.loop == "fast" and "wave_has_hit" in src_text:
+            # the hit path's blocks: behind the loop, up to the last branch back into it
+            def tgt(x):
+                off = int(x[2].split()[0])
+                return x[0] + 4 + 4 * (off - 65536 if off >= 32768 else off)
+            back = [j for j in range(hi + 1, len(insts)) if insts[j][1].startswith(("s_cbranch", "s_branch")) and
+                    insts[lo][0] <= tgt(insts[j]) <= insts[hi][0]]
+            if back:
+                loop = insts[lo:max(back) + 1]
+                print("hit path: %d instructions behind the loop" % (len(loop) - n_hot))
         chains = symbolize(obj, [x[0] for x in loop])
     marks = line_marks(src_text)
+    gated = a.loop == "fast" and "wave_has_hit" in src_text  # (a source with the gate, in a specialised loop)
 
-    def phase_of(chain):
+    def phase_of(chain, cold=False):
+        ph = phase_of_chain(chain)
+        return ph + HIT_TAG if cold and RARE_TAG not in ph else ph
+
+    def phase_of_chain(chain):
         outer = list(reversed(chain))  # kernel first
         names = [f for f, _ in outer]
         for fn in names:
@@ -261,30 +290,43 @@ def main():
     per = collections.defaultdict(collections.Counter)
     cls = collections.defaultdict(collections.Counter)  # VALU issue classes (tools/issue_model.classify)
     prev_vcc = False
-    for (addr, mn, ops, size), ch in zip(loop, chains):
-        ph = phase_of(ch)
+    for i, ((addr, mn, ops, size), ch) in enumerate(zip(loop, chains)):
+        ph = phase_of(ch, cold=i >= n_hot)
         per[ph][kind(mn)] += 1
         if mn.startswith("v_") and not mn.startswith(("v_readfirstlane", "v_readlane", "v_writelane", "v_mfma")):
             cls[ph][IM.classify(mn, ops, size, prev_vcc)] += 1
             prev_vcc = IM.reads_vcc(mn, ops)
     ticks = 2  # the main loop is the row loop unrolled by two ticks
-    rows, common, rare = [], collections.Counter(), collections.Counter()
+    rows, common, rare, hit_only = [], collections.Counter(), collections.Counter(), collections.Counter()
     for ph, c in per.items():
         tot = sum(c.values())
         row = {"phase": ph, "per_tick": {k: v / ticks for k, v in sorted(c.items())}, "total_per_tick": tot / ticks,
-               "valu_classes_per_tick": {k: v / ticks for k, v in sorted(cls[ph].items())}, "rare": RARE_TAG in ph}
+               "valu_classes_per_tick": {k: v / ticks for k, v in sorted(cls[ph].items())}, "rare": RARE_TAG in ph,
+               "hit_path_only": ph.endswith(HIT_TAG)}
         rows.append(row)
         (rare if row["rare"] else common).update(c)
-    rows.sort(key=lambda r: (r["rare"], -r["per_tick"].get("valu", 0), -r["total_per_tick"]))
+        if row["hit_path_only"]:
+            hit_only.update(c)
+    rows.sort(key=lambda r: (r["rare"], r["hit_path_only"], -r["per_tick"].get("valu", 0), -r["total_per_tick"]))
+    # with the gate, the common path is the no-hit path (what about nine wave-ticks in ten run, and what
+    # the per-wave-tick counters mostly measure); the hit path adds the [hit] phases to it
+    hit_path = common
+    common = no_hit = common - hit_only
     res = {"kernel": a.kernel, "loop": a.loop, "source": os.path.relpath(a.src, ROOT), "flags": "build.py flags_for(fs_kernels.hip) + -gline-tables-only "
            "(same code as the library: mnemonic sequence checked)",
            "loop_instructions": len(loop), "ticks_in_loop": ticks,
            "common_path_per_tick": {k: v / ticks for k, v in sorted(common.items())},
+           "no_hit_path_per_tick": {k: v / ticks for k, v in sorted(no_hit.items())},
+           "hit_path_per_tick": {k: v / ticks for k, v in sorted(hit_path.items())},
+           "hit_gate": gated,
            "rare_paths_per_tick_static": {k: v / ticks for k, v in sorted(rare.items())},
            "phases": rows,
            "note": "static counts of the main loop (two ticks) / 2, charged by inline chain; rare phases run only "
                    "on waves with a hit / KO lane, and the common-path counts are the ones to compare with the "
-                   "measured per-wave-tick SQ counters"}
+                   "measured per-wave-tick SQ counters.  With hit_gate true the common path is the no-hit path "
+                   "(no_hit_path_per_tick, the same figures), hit_path_per_tick adds the [hit] phases, which run on "
+                   "the wave-ticks with a hit (about 12 % of a rollout's), and the counters measure the mix of the "
+                   "two; loop_instructions then counts the loop's span and the hit path's blocks behind it"}
     if a.sq:
         with open(a.sq) as f:
             sq = json.load(f)
@@ -299,7 +341,11 @@ def main():
             r["phase"][:82], r["per_tick"].get("valu", 0), r["per_tick"].get("salu", 0), r["per_tick"].get("lds", 0),
             r["per_tick"].get("vmem", 0), r["total_per_tick"], vc.get("vopc", 0), vc.get("vop3_op", 0),
             vc.get("fast", 0)))
-    print("common path per tick:", res["common_path_per_tick"])
+    print("common path per tick%s:" % (" (the no-hit path)" if gated else ""), res["common_path_per_tick"], "total",
+          sum(common.values()) / ticks)
+    if gated:
+        print("hit path per tick (the no-hit path + the [hit] phases):", res["hit_path_per_tick"], "total",
+              sum(hit_path.values()) / ticks)
     if a.json:
         with open(a.json, "w") as f:
             json.dump(res, f, indent=1)
