@@ -20,7 +20,8 @@
 // Paths: BC = Assets/Script/BattleCore.cs, F = Assets/Script/Fighter.cs, AI = Assets/Script/BattleAI.cs,
 // FE = footsies-gym/footsies_gym/envs/footsies.py.
 
-// P2's whole BattleAI on the arena's lane (the two-lane kernel splits its queues over the pair)
+// P2's whole BattleAI on the arena's lane (the two-lane kernel splits its queues over the pair).
+// (decoded with the kBot* positions, not through unpack_bot: deliberate, DESIGN.md "The identity rule")
 struct Bot1 {
   uint4 rng;                          // the game's UnityEngine.Random
   uint32_t mplan, midx, aplan, aidx;  // plans stored + 1 (0 = empty queue), dequeued counts
@@ -85,7 +86,7 @@ __device__ __forceinline__ uint32_t bot_next_input1(Bot1& b, float dist, uint32_
 struct Arena1 {
   Fighter f0, f1;
   int frame_count;
-  uint32_t rec_count;
+  uint32_t rec_count;     // the header word's fields (Header), but p2bot: the handle kind gives it
   uint32_t rec0, rec1;    // recordingP1/P2Input[index - 1]
   uint32_t act0, act1;    // the remote actors' inputs (TrainingRemoteActor.input)
   uint32_t bin;           // P2 bot's input (TrainingBattleAIActor.input), bot handles
@@ -108,26 +109,26 @@ __device__ __forceinline__ void load_arena1(Arena1& A, const DevState& s, int a)
   A.f1.x = pos.y;
   A.f0.hist = hist.x;
   A.f1.hist = hist.y;
-  const uint32_t h = (uint32_t)aw.y;
+  const Header H = unpack_header((uint32_t)aw.y);
   A.frame_count = aw.x;
-  A.rec_count = h & 0x7fff;
-  A.rec0 = (h >> 15) & 7;
-  A.rec1 = (h >> 18) & 7;
-  A.act0 = (h >> 21) & 7;
-  A.act1 = (h >> 24) & 7;
-  A.pending = (h >> 27) & 1;
-  A.has_term = (h >> 28) & 1;
+  A.rec_count = H.rec_count;
+  A.rec0 = H.rec[0];
+  A.rec1 = H.rec[1];
+  A.act0 = H.act[0];
+  A.act1 = H.act[1];
+  A.pending = H.pending;
+  A.has_term = H.has_term;
   A.bin = 0;
   if constexpr (V == FS_P2_BOT) {
     A.bot.rng = s.rng[a];
     const uint2 b = s.bot[a];
-    A.bot.mplan = b.x & 7;
-    A.bot.midx = (b.x >> 3) & 127;
-    A.bot.aplan = (b.x >> 10) & 7;
-    A.bot.aidx = (b.x >> 13) & 127;
-    A.bot.prev_opp = (b.x >> 20) & 31;
+    A.bot.mplan = (b.x >> kBotMoveQueue) & 7;
+    A.bot.midx = (b.x >> kBotMoveIdx) & 127;
+    A.bot.aplan = (b.x >> kBotAtkQueue) & 7;
+    A.bot.aidx = (b.x >> kBotAtkIdx) & 127;
+    A.bot.prev_opp = (b.x >> kBotPrevOpp) & 31;
     A.bot.prev_dist = __uint_as_float(b.y);
-    A.bin = (b.x >> 26) & 7;  // (a bot-created P2 is Reset at every Intro: always ready)
+    A.bin = (b.x >> kBotInput) & 7;  // (a bot-created P2 is Reset at every Intro: always ready)
   }
 }
 
@@ -137,17 +138,15 @@ __device__ __forceinline__ void store_arena1(const Arena1& A, const DevState& s,
   s.pos[a] = make_float2(A.f0.x, A.f1.x);
   s.hist[a] = make_uint2(A.f0.hist, A.f1.hist);
   s.fpk[a] = make_uint4((uint32_t)w0, (uint32_t)(w0 >> 32), (uint32_t)w1, (uint32_t)(w1 >> 32));
-  const uint32_t p2bot = V == FS_P2_BOT ? 1u : 0u;
-  const uint32_t h = A.rec_count | (A.rec0 << 15) | (A.rec1 << 18) | (A.act0 << 21) | (A.act1 << 24) |
-                     (A.pending << 27) | (A.has_term << 28) | (p2bot << 29);
-  s.aw[a] = make_int2(A.frame_count, (int)h);
+  const Header H{A.rec_count, {A.rec0, A.rec1}, {A.act0, A.act1}, A.pending, A.has_term, V == FS_P2_BOT ? 1u : 0u};
+  s.aw[a] = make_int2(A.frame_count, (int)pack_header(H));
   s.cum[a] = A.cum;
   if constexpr (V == FS_P2_BOT) {
     const Bot1& b = A.bot;
     s.rng[a] = b.rng;
-    s.bot[a] = make_uint2(b.mplan | (b.midx << 3) | (b.aplan << 10) | (b.aidx << 13) | (b.prev_opp << 20) |
-                              (1u << 25) | (A.bin << 26),
-                          __float_as_uint(b.prev_dist));
+    const uint32_t w = (b.mplan << kBotMoveQueue) | (b.midx << kBotMoveIdx) | (b.aplan << kBotAtkQueue) |
+                       (b.aidx << kBotAtkIdx) | (b.prev_opp << kBotPrevOpp) | (1u << kBotReady) | (A.bin << kBotInput);
+    s.bot[a] = make_uint2(w, __float_as_uint(b.prev_dist));
   }
 }
 
@@ -177,18 +176,10 @@ __device__ __forceinline__ void push_character_vs_character1(Fighter& f0, Fighte
   apply_position_change<FM>(f1, dx1);
 }
 
-// The resolution entry's nibble for overlap mask m: the outcome at the attacker's hit count (low
-// nibble) and at 0 (high), as hitbox_hurtbox_collision picks it
-__device__ __forceinline__ uint32_t resolve_byte(U4 res, uint32_t m) {
-  const uint32_t sel = (m & 7u) | 0x0c0c0c00u;
-  const uint32_t lo = __builtin_amdgcn_perm(res.y, res.x, sel), hi = __builtin_amdgcn_perm(res.w, res.z, sel);
-  return (m & 8u) ? hi : lo;
-}
-
 // UpdateHitboxHurtboxCollision (BC:521-591) for both phases on one lane: phase A (P1 attacks, P2
 // defends) at P1's hit count, phase B (P2 attacks P1) at P2's hit count after phase A (0 if A hit,
 // SetCurrentAction), then the defenders' NotifyDamaged, the attackers' NotifyAttackHit, the
-// proximity latches and SetHitStun on both fighters, in hitbox_hurtbox_collision's order.
+// proximity latches and SetHitStun on both fighters, in collision_resolve's order.
 template <int FM>
 __device__ __forceinline__ void hitbox_hurtbox_collision1(Fighter& f0, Fighter& f1, const RecGeo& R0,
                                                           const RecGeo& R1, U4 resA, U4 resB, uint32_t ymA,
@@ -202,7 +193,7 @@ __device__ __forceinline__ void hitbox_hurtbox_collision1(Fighter& f0, Fighter& 
   const bool hit0 = (tB & 1u) != 0, hit1 = hitA != 0;  // P1 is phase B's defender, P2 phase A's
   f0.hits += (int)hitA;                                // NotifyAttackHit for P1 (F:352-355)
   int stun0 = 0, stun1 = 0;
-  if (hit0) {
+  if (hit0) {  // (NotifyDamaged and the stun, written out per site: deliberate, DESIGN.md "The identity rule")
     const AttackInfo ad = attack_info((int)((tB >> 1) & 3u));
     const int res = notify_damaged(f0, ad);
     stun0 = res == DR_GUARD ? ad.guard_stun : res == DR_GUARD_BREAK ? ad.guard_break_stun : ad.hit_stun;
@@ -246,22 +237,15 @@ __device__ __forceinline__ void reset_burst1(Arena1& A, bool after_ko) {
     A.rec1 = in1;
     A.rec_count++;
   }
-  auto intro = [](Fighter& f, uint32_t in, int k) {
-    const uint32_t r = rel_bits(in, k);
-    f.hist = (r & 1) | ((r & 2) << 15);
-    f.hold = (in & IN_ATTACK) ? 1 : 0;
-    const bool stunned = f.stun > 0;
-    f.stun -= stunned ? 1 : 0;
-    f.frame = stunned ? 0 : 1;
-  };
-  intro(A.f0, in0, 0);
-  intro(A.f1, in1, 1);
+  intro_tick(A.f0, in0, 0);
+  intro_tick(A.f1, in1, 1);
   A.frame_count = -1;
   A.rec_count = 0;
   if constexpr (BOT) A.bin = bot_next_input1(A.bot, bot_distance<FM>(x1, x2), p1_act, bot_prefetch1(A.bot));
 }
 
 // outputs (FE:336-380, 537-549): a lane stores both fighters' values of each [N][2] array at once
+// (the DEAD / WIN remap and move_frame restate write_obs: deliberate, DESIGN.md "The identity rule")
 __device__ __forceinline__ uint32_t obs_move(const Fighter& f) {
   const int a = f.act;
   return (a == A_DEAD || a == A_WIN) ? (uint32_t)A_STAND : (uint32_t)a;  // FE:537-549
@@ -351,8 +335,8 @@ __device__ __forceinline__ void env_step1(Arena1& A, uint32_t a1, uint32_t a2, c
     A.pending = 0;
     A.has_term = 0;
     A.cum = 0.0;
-    A.te0 = tick_entry_after_burst(A.f0);
-    A.te1 = tick_entry_after_burst(A.f1);
+    A.te0 = tick_entry(A.f0);  // (STAND at frame 0 or 1, hitstun surviving: SetupBattleStart keeps it)
+    A.te1 = tick_entry(A.f1);
     settle2<WAIT>(n1, n2);
     if constexpr (PK) {
       write_packed1(A, o.pk_lanes, r, 0u);
@@ -442,8 +426,8 @@ __device__ __forceinline__ void env_step1(Arena1& A, uint32_t a1, uint32_t a2, c
       reset_burst1<FM, P2>(A, true);
       A.cum = 0.0;
       A.has_term = 0;
-      A.te0 = tick_entry_after_burst(A.f0);
-      A.te1 = tick_entry_after_burst(A.f1);
+      A.te0 = tick_entry(A.f0);  // (STAND at frame 0 or 1, hitstun surviving)
+      A.te1 = tick_entry(A.f1);
     } else {
       A.pending = 1;
       A.has_term = 1;

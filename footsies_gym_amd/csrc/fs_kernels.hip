@@ -8,27 +8,28 @@
 //   load (coalesced 4/8/16-B per lane) -> n ticks in registers -> store
 //
 // Frame data is one 35 KB image (fs_tables.h), staged into LDS per block by the fused launches
-// and read in place from global memory by the one-tick launch: per action a 16-B ActionInfo
-// (frame count, loop, cancel window), per (action, frame) an index into 53 de-duplicated frame
-// records (three 16-B entries of x geometry and velocity) -- the window scans of
-// ActionData.cs:87-168 resolved offline (tools/gen_tables.py) -- the request chain's outcome per
-// (action, window state, inputs), the box-pair y overlaps per record pair and the hit resolution
-// per (attacker hit count, attacker record) -- and, for the fused launches, one 16-bit tick entry
-// per (action, in hitstun?, frame): the next tick's frame, its frame record and its request class
-// (IncrementActionFrame and the cancel-window tests resolved offline too).  A fused tick's
-// dependent LDS round trips: the tick entry (issued after the previous tick's collision), then
-// the request-table entry, then the frame record with the y-overlap bits and the resolution
-// entry; the one-tick launch carries ActionInfo instead and reads the record index with the
-// request-table entry.  The
-// 180-deep input histories
-// (Fighter.cs:98-101) are two 16-frame shift registers (backward / forward relative to the
-// fighter's facing) plus a saturating attack-hold counter: the reference
-// only reads input[0..16] for dashes (Fighter.cs:585-635, dashAllowFrame 9) and
-// "attack held on input[1..59]" for the charge special (Fighter.cs:569-583).
+// and read in place from global memory by the one-tick launch.  It holds, with the window scans of
+// ActionData.cs:87-168 resolved offline (tools/gen_tables.py): per action a 16-B ActionInfo (frame
+// count, loop, cancel window); per (action, frame) an index into 53 de-duplicated frame records
+// (three 16-B entries of x geometry and velocity); the request chain's outcome per (action, window
+// state, inputs); the box-pair y overlaps per record pair; the hit resolution per (attacker hit
+// count, attacker record); and one 16-bit tick entry per (action, in hitstun?, frame): the next
+// tick's frame, its frame record and its request class (IncrementActionFrame and the cancel-window
+// tests resolved offline too).
 //
-// Float arithmetic follows the C# expression order with every binary32
-// operation rounded (__fadd_rn/__fmul_rn; the file is also built with
-// -ffp-contract=off) or, in FS_FLOAT_DOUBLE mode, with binary64 temporaries.
+// The fused launches carry the tick entry from tick to tick (Lane::te, read after the previous
+// tick's collision); a fused tick's dependent LDS round trips are then the request-table entry, and
+// the frame record with the y-overlap bits and the resolution entry.  The one-tick launch (k_step)
+// carries ActionInfo instead (Lane::ai) and reads the record index with the request-table entry.
+//
+// Input histories.  The 180-deep histories (Fighter.cs:98-101) are two 16-frame shift registers
+// (backward / forward relative to the fighter's facing) plus a saturating attack-hold counter: the
+// reference only reads input[0..16] for dashes (Fighter.cs:585-635, dashAllowFrame 9) and "attack
+// held on input[1..59]" for the charge special (Fighter.cs:569-583).
+//
+// Float arithmetic follows the C# expression order with every binary32 operation rounded
+// (__fadd_rn/__fmul_rn; the file is also built with -ffp-contract=off) or, in FS_FLOAT_DOUBLE mode,
+// with binary64 temporaries.
 //
 // Paths: BC = Assets/Script/BattleCore.cs, F = Assets/Script/Fighter.cs,
 // AI = Assets/Script/BattleAI.cs, FE = footsies-gym/footsies_gym/envs/footsies.py.
@@ -77,13 +78,7 @@ constexpr int kTabLds = 0, kTabGlobal = 1;
 //   [21,23) guard | [23,25) hit count | [25,30) buffer idx | [30,35) reserve idx |
 //   35 isInputBackward | 36 isReserveProximityGuard | 37 hasWon | [38,44) attack hold |
 //   44 facing flipped (isFaceRight != isPlayerOne, only after a state load)
-// arena header word (DevState::aw.y)
-//   [0,15) recording count | [15,18) rec P1 | [18,21) rec P2 | [21,24) remote actor P1 input |
-//   [24,27) remote actor P2 input | 27 reset pending | 28 has_terminated | 29 P2's actor is the bot
-// bot word (DevState::bot.x for P2's BattleAI, DevState::bot1.x for P1's)
-//   [0,3) move plan+1 (0 = empty) | [3,10) move index | [10,13) attack plan+1 |
-//   [13,20) attack index | [20,25) previous FightState opponent action idx |
-//   25 ready (fightStates[5] set) | [26,29) the bot actor's last input (TrainingBattleAIActor.input)
+// (the arena header word: struct Header; the bot word: the kBot* positions at unpack_bot)
 // ---------------------------------------------------------------------------
 
 // A pair of like box values (the x of box 0 and 1, or their half-widths): <2 x float> arithmetic is
@@ -107,14 +102,35 @@ struct Fighter {
   float py, uy0, uy1, hy0, hy1;  // world y (rect.y) of the pushbox, hurtboxes 0 / 1, hitboxes 0 / 1
 };
 
+// The arena header word (DevState::aw.y); this is the one home of its layout:
+//   [0,15) recording count | [15,18) rec P1 | [18,21) rec P2 | [21,24) remote actor P1 input |
+//   [24,27) remote actor P2 input | 27 reset pending | 28 has_terminated | 29 P2's actor is the bot
+// (load_lane / store_lane pick one player's fields with a lane-dependent shift of these positions)
+constexpr uint32_t kHdrRecCountMask = 0x7fff;
+constexpr int kHdrRec1 = 15, kHdrRec2 = 18, kHdrAct1 = 21, kHdrAct2 = 24;
+constexpr int kHdrPending = 27, kHdrHasTerm = 28, kHdrP2Bot = 29;
+struct Header {
+  uint32_t rec_count;          // recording index
+  uint32_t rec[2], act[2];     // per player: recordingPnInput[index - 1], the remote actor's input
+  uint32_t pending, has_term;  // 0 / 1
+  uint32_t p2bot;              // 0 / 1
+};
+__device__ __forceinline__ Header unpack_header(uint32_t h) {
+  return Header{h & kHdrRecCountMask, {(h >> kHdrRec1) & 7, (h >> kHdrRec2) & 7},
+                {(h >> kHdrAct1) & 7, (h >> kHdrAct2) & 7}, (h >> kHdrPending) & 1, (h >> kHdrHasTerm) & 1,
+                (h >> kHdrP2Bot) & 1};
+}
+__device__ __forceinline__ uint32_t pack_header(const Header& H) {
+  return H.rec_count | (H.rec[0] << kHdrRec1) | (H.rec[1] << kHdrRec2) | (H.act[0] << kHdrAct1) |
+         (H.act[1] << kHdrAct2) | (H.pending << kHdrPending) | (H.has_term << kHdrHasTerm) | (H.p2bot << kHdrP2Bot);
+}
+
 struct Arena {
   Fighter f0, f1;
   int frame_count;
-  uint32_t rec_count, rec1, rec2, act1, act2;
-  bool pending, has_term;
+  Header h;
   double cum;
   uint4 rng;
-  bool p2bot;
   uint2 bw[2];  // bot words of P1's and P2's BattleAI (decoded by the state kernels)
 };
 
@@ -158,15 +174,7 @@ __device__ __forceinline__ void load_arena(Arena& A, const DevState& s, int i) {
   A.f0.hist = hist.x;  // split form (get/set convert)
   A.f1.hist = hist.y;
   A.frame_count = aw.x;
-  uint32_t h = (uint32_t)aw.y;
-  A.rec_count = h & 0x7fff;
-  A.rec1 = (h >> 15) & 7;
-  A.rec2 = (h >> 18) & 7;
-  A.act1 = (h >> 21) & 7;
-  A.act2 = (h >> 24) & 7;
-  A.pending = (h >> 27) & 1;
-  A.has_term = (h >> 28) & 1;
-  A.p2bot = (h >> 29) & 1;
+  A.h = unpack_header((uint32_t)aw.y);
   A.rng = s.rng[i];
   A.bw[0] = s.bot1[i];
   A.bw[1] = s.bot[i];
@@ -178,9 +186,7 @@ __device__ __forceinline__ void store_arena(const Arena& A, const DevState& s, i
   s.posy[i] = make_float2(A.f0.y, A.f1.y);
   s.hist[i] = make_uint2(A.f0.hist, A.f1.hist);
   s.fpk[i] = make_uint4((uint32_t)w0, (uint32_t)(w0 >> 32), (uint32_t)w1, (uint32_t)(w1 >> 32));
-  uint32_t h = A.rec_count | (A.rec1 << 15) | (A.rec2 << 18) | (A.act1 << 21) | (A.act2 << 24) |
-               ((uint32_t)A.pending << 27) | ((uint32_t)A.has_term << 28) | ((uint32_t)A.p2bot << 29);
-  s.aw[i] = make_int2(A.frame_count, (int)h);
+  s.aw[i] = make_int2(A.frame_count, (int)pack_header(A.h));
   s.cum[i] = A.cum;
   s.rng[i] = A.rng;
   s.bot1[i] = A.bw[0];
@@ -457,8 +463,6 @@ __device__ __forceinline__ uint32_t tick_entry(const Fighter& f) {  // f.frame <
   const uint32_t off = (stunned << 7) | (((uint32_t)f.act << 8) | ((uint32_t)f.frame << 1));
   return *reinterpret_cast<const uint16_t*>(reinterpret_cast<const char*>(&sT.tick[0][0][0]) + off);
 }
-// (after a reset burst: STAND at frame 0 or 1, hitstun surviving -- SetupBattleStart keeps it)
-__device__ __forceinline__ uint32_t tick_entry_after_burst(const Fighter& f) { return tick_entry(f); }
 // The same word for any frame, from ActionInfo and rec_index (the arithmetic k_step runs every
 // tick; tools/gen_tables.py proves the two equal): the frame field is as wide as the frame.
 __device__ __forceinline__ uint32_t tick_entry_slow(const Fighter& f) {
@@ -900,21 +904,30 @@ struct FullBot {
   bool ready;                         // fightStates[5] != null
 };
 
+// The bot word (DevState::bot for P2's BattleAI, DevState::bot1 for P1's); this is the one home of
+// its layout.  .x: two 10-bit queue fields, each [0,3) plan+1 (0 = empty) | [3,10) index --
+//   [0,10) movement queue | [10,20) attack queue | [20,25) previous FightState opponent action idx |
+//   25 ready (fightStates[5] set) | [26,29) the bot actor's last input (TrainingBattleAIActor.input)
+// .y: the previous FightState's distance.  (load_lane / store_lane pick the lane's own queue field.)
+constexpr int kBotQueueIdx = 3;  // within a queue field
+constexpr int kBotMoveQueue = 0, kBotAtkQueue = 10, kBotPrevOpp = 20, kBotReady = 25, kBotInput = 26;
+constexpr int kBotMoveIdx = kBotMoveQueue + kBotQueueIdx, kBotAtkIdx = kBotAtkQueue + kBotQueueIdx;
 __device__ __forceinline__ FullBot unpack_bot(uint2 w, uint32_t& input) {
   FullBot b;
-  b.mplan = w.x & 7;
-  b.midx = (w.x >> 3) & 127;
-  b.aplan = (w.x >> 10) & 7;
-  b.aidx = (w.x >> 13) & 127;
-  b.prev_opp = (w.x >> 20) & 31;
-  b.ready = (w.x >> 25) & 1;
-  input = (w.x >> 26) & 7;
+  b.mplan = (w.x >> kBotMoveQueue) & 7;
+  b.midx = (w.x >> kBotMoveIdx) & 127;
+  b.aplan = (w.x >> kBotAtkQueue) & 7;
+  b.aidx = (w.x >> kBotAtkIdx) & 127;
+  b.prev_opp = (w.x >> kBotPrevOpp) & 31;
+  b.ready = (w.x >> kBotReady) & 1;
+  input = (w.x >> kBotInput) & 7;
   b.prev_dist = __uint_as_float(w.y);
   return b;
 }
 __device__ __forceinline__ uint2 pack_bot(const FullBot& b, uint32_t input) {
-  return make_uint2(b.mplan | (b.midx << 3) | (b.aplan << 10) | (b.aidx << 13) | (b.prev_opp << 20) |
-                        ((uint32_t)b.ready << 25) | (input << 26),
+  return make_uint2((b.mplan << kBotMoveQueue) | (b.midx << kBotMoveIdx) | (b.aplan << kBotAtkQueue) |
+                        (b.aidx << kBotAtkIdx) | (b.prev_opp << kBotPrevOpp) | ((uint32_t)b.ready << kBotReady) |
+                        (input << kBotInput),
                     __float_as_uint(b.prev_dist));
 }
 
@@ -1024,21 +1037,23 @@ __device__ __forceinline__ void load_lane(Lane& L, const DevState& s, int a, uin
   unpack_fighter(L.f, w.x, w.y);
   const uint32_t h = (uint32_t)aw.y;
   L.frame_count = aw.x;
-  L.rec_count = h & 0x7fff;
-  L.rec = (h >> (k ? 18 : 15)) & 7;
-  L.act = (h >> (k ? 24 : 21)) & 7;
-  L.pending = (h >> 27) & 1;
-  L.has_term = (h >> 28) & 1;
-  L.p2bot = (h >> 29) & 1;
+  // (a lane-dependent shift, not unpack_header and a select: deliberate, DESIGN.md "The identity rule")
+  L.rec_count = h & kHdrRecCountMask;
+  L.rec = (h >> (k ? kHdrRec2 : kHdrRec1)) & 7;
+  L.act = (h >> (k ? kHdrAct2 : kHdrAct1)) & 7;
+  L.pending = (h >> kHdrPending) & 1;
+  L.has_term = (h >> kHdrHasTerm) & 1;
+  L.p2bot = (h >> kHdrP2Bot) & 1;
   L.bin = 0;
   if constexpr (V == FS_P2_BOT) {  // both lanes read the same 24 B (one cache line); P2 uses it
     L.bot.rng = s.rng[a];
     const uint2 b = s.bot[a];
-    L.bot.plan = k ? (b.x & 7) : ((b.x >> 10) & 7);  // P2 lane: movement queue, P1 lane: attack queue
-    L.bot.idx = k ? ((b.x >> 3) & 127) : ((b.x >> 13) & 127);
-    L.bot.prev_opp = (b.x >> 20) & 31;
+    // P2 lane: movement queue, P1 lane: attack queue (the split decode, as for the header)
+    L.bot.plan = k ? ((b.x >> kBotMoveQueue) & 7) : ((b.x >> kBotAtkQueue) & 7);
+    L.bot.idx = k ? ((b.x >> kBotMoveIdx) & 127) : ((b.x >> kBotAtkIdx) & 127);
+    L.bot.prev_opp = (b.x >> kBotPrevOpp) & 31;
     L.bot.prev_dist = __uint_as_float(b.y);
-    L.bin = (b.x >> 26) & 7;  // (a bot-created P2 is Reset at every Intro: always ready)
+    L.bin = (b.x >> kBotInput) & 7;  // (a bot-created P2 is Reset at every Intro: always ready)
   } else if constexpr (V == kActors) {
     L.rng = s.rng[a];
     L.fb = unpack_bot(k ? s.bot[a] : s.bot1[a], L.bin);
@@ -1055,17 +1070,19 @@ __device__ __forceinline__ void store_lane(const Lane& L, const DevState& s, int
   const uint32_t other = xpair(L.rec | (L.act << 3));  // P2's recorded/actor input for the header
   if (L.k == 0) {
     const uint32_t p2bot = V == FS_P2_BOT ? 1u : V == kActors ? (uint32_t)L.p2bot : 0u;
-    const uint32_t h = L.rec_count | (L.rec << 15) | ((other & 7) << 18) | (L.act << 21) | ((other >> 3) << 24) |
-                       ((uint32_t)L.pending << 27) | ((uint32_t)L.has_term << 28) | (p2bot << 29);
+    const uint32_t h = L.rec_count | (L.rec << kHdrRec1) | ((other & 7) << kHdrRec2) | (L.act << kHdrAct1) |
+                       ((other >> 3) << kHdrAct2) | ((uint32_t)L.pending << kHdrPending) |
+                       ((uint32_t)L.has_term << kHdrHasTerm) | (p2bot << kHdrP2Bot);
     s.aw[a] = make_int2(L.frame_count, (int)h);
     s.cum[a] = L.cum;
   }
   if constexpr (V == FS_P2_BOT) {
     const Bot& b = L.bot;
-    const uint32_t mine = b.plan | (b.idx << 3), other = xpair(mine);  // the partner's queue
+    const uint32_t mine = b.plan | (b.idx << kBotQueueIdx), other = xpair(mine);  // the partner's queue
     if (L.k == 1) {
       s.rng[a] = b.rng;
-      s.bot[a] = make_uint2(mine | (other << 10) | (b.prev_opp << 20) | (1u << 25) | (L.bin << 26),
+      s.bot[a] = make_uint2((mine << kBotMoveQueue) | (other << kBotAtkQueue) | (b.prev_opp << kBotPrevOpp) |
+                                (1u << kBotReady) | (L.bin << kBotInput),
                             __float_as_uint(b.prev_dist));
     }
   } else if constexpr (V == kActors) {
@@ -1159,6 +1176,13 @@ __device__ __forceinline__ AttackInfo attack_info(int i) {
 // overlap mask) holds the outcome at the attacker's hit count o_hits (low nibble) and at 0 (high).
 // The lookup, then what the outcome does (collision_lookup / collision_resolve: the specialised row
 // loops put a wave-wide gate between the two, see env_step).
+// The entry's byte for overlap mask m, picked by v_perm_b32 (selector byte m & 7 of the low or high
+// 8 bytes; selector 0x0c = zero)
+__device__ __forceinline__ uint32_t resolve_byte(U4 res, uint32_t m) {
+  const uint32_t sel = (m & 7u) | 0x0c0c0c00u;
+  const uint32_t lo = __builtin_amdgcn_perm(res.y, res.x, sel), hi = __builtin_amdgcn_perm(res.w, res.z, sel);
+  return (m & 8u) ? hi : lo;
+}
 template <int FM>
 __device__ __forceinline__ uint32_t collision_lookup(const Fighter& f, F4 my_hurt, float o_hw0, float o_hw1, U4 res,
                                                      uint32_t ym) {
@@ -1166,14 +1190,9 @@ __device__ __forceinline__ uint32_t collision_lookup(const Fighter& f, F4 my_hur
   const float o_hx0 = xpair(f.hx0), o_hx1 = xpair(f.hx1);
   const uint32_t xm = box_x_overlaps<FM>(o_hw0, o_hw1, o_hx0, o_hx1, my_hurt.zw, F2{f.ux0, f.ux1});
   // phase A (P1 attacks P2) is resolved on the P2 lane; its outcome crosses to P1, whose lane
-  // then resolves phase B (P2 attacks P1) with P2's hit count after phase A
-  // the resolution for both phases from one byte of the attacker's entry (kTables.resolve,
-  // tools/gen_tables.py), picked by v_perm_b32 (selector byte m & 7 of the low or high 8 bytes;
-  // selector 0x0c = zero)
-  const uint32_t m = xm & ym;
-  const uint32_t sel = (m & 7u) | 0x0c0c0c00u;
-  const uint32_t lo = __builtin_amdgcn_perm(res.y, res.x, sel), hi = __builtin_amdgcn_perm(res.w, res.z, sel);
-  return (m & 8u) ? hi : lo;
+  // then resolves phase B (P2 attacks P1) with P2's hit count after phase A: both phases from one
+  // byte of the attacker's entry (kTables.resolve, tools/gen_tables.py)
+  return resolve_byte(res, xm & ym);
 }
 // `tab`: collision_lookup's byte.
 __device__ __forceinline__ void collision_resolve(Fighter& f, uint32_t k, uint32_t tab) {
@@ -1193,7 +1212,7 @@ __device__ __forceinline__ void collision_resolve(Fighter& f, uint32_t k, uint32
   // P2 its NotifyDamaged (A) before NotifyAttackHit (B).
   f.hits += k == 0 ? (int)hitA : 0;  // NotifyAttackHit for P1 (F:352-355)
   int my_stun = 0;
-  if (my_hit) {
+  if (my_hit) {  // (written out here and twice in fs_arena1.h: deliberate, DESIGN.md "The identity rule")
     const AttackInfo ad = attack_info(my_atk);
     const int res = notify_damaged(f, ad);
     my_stun = res == DR_GUARD ? ad.guard_stun : res == DR_GUARD_BREAK ? ad.guard_break_stun : ad.hit_stun;
@@ -1225,12 +1244,6 @@ __device__ __forceinline__ bool wave_has_hit(uint32_t tab) {
 // The no-hit path's whole effect: NotifyInProximityGuardRange (F:400-406), my_prox from the low nibble
 __device__ __forceinline__ void proximity_latch(Fighter& f, uint32_t tab) { f.prox |= (tab >> 3) & 1u & f.in_back; }
 
-template <int FM>
-__device__ __forceinline__ void hitbox_hurtbox_collision(Fighter& f, uint32_t k, F4 my_hurt, float o_hw0, float o_hw1,
-                                                         U4 res, uint32_t ym) {
-  collision_resolve(f, k, collision_lookup<FM>(f, my_hurt, o_hw0, o_hw1, res, ym));
-}
-
 // KO tick -> End (winner), End tick (BC:221-243, 306-325, 371-381), reduced to
 // its observable effects.  SetupBattleStart (next tick) overwrites position,
 // action, frame, hit count, buffer, reserve, vital, guard, hasWon and the input
@@ -1260,15 +1273,6 @@ __device__ __forceinline__ void setup_battle_start(Fighter& f, float x) {
   set_action(f, A_STAND);
 }
 
-// The reset burst of one lane (BC:212-345).  after_ko: the KO -> End -> Stop ->
-// Intro -> Fight sequence after a terminal frame (ClearInput already applied);
-// otherwise the RESET / game-start path Stop -> Intro -> Fight.
-//   Intro tick: the stale actor input enters the cleared history, the frame
-//   advances unless in hitstun, RequestAction(STAND) on STAND is a no-op, and
-//   movement / boxes / pushes are no-ops (STAND has no movement window; base
-//   pushboxes at x = -2 / +2 neither overlap nor touch the stage edges).
-//   Fight: frameCount = -1, recording index 0, state(-1) emitted, and the bot's
-//   first RequestNextInput.
 // The handle's actors, for kActors (StepParams / ResetParams).
 struct Actors {
   bool p1_bot;     // FS_P1_BOT
@@ -1326,6 +1330,15 @@ __device__ __forceinline__ void actors_request(Lane& L, const Actors& ac, float 
 //   pushboxes at x = -2 / +2 neither overlap nor touch the stage edges).
 //   Fight: frameCount = -1, recording index 0, state(-1) emitted, and the bots'
 //   first RequestNextInput.
+// The Intro tick of fighter k, with actor input `in`:
+__device__ __forceinline__ void intro_tick(Fighter& f, uint32_t in, int k) {
+  const uint32_t r = rel_bits(in, k);
+  f.hist = (r & 1) | ((r & 2) << 15);
+  f.hold = (in & IN_ATTACK) ? 1 : 0;
+  const bool stunned = f.stun > 0;
+  f.stun -= stunned ? 1 : 0;
+  f.frame = stunned ? 0 : 1;
+}
 template <int FM, int V, bool G = false>
 __device__ __forceinline__ void reset_burst(Lane& L, bool after_ko, const Actors& ac) {
   constexpr bool BOT = V == FS_P2_BOT;
@@ -1351,12 +1364,7 @@ __device__ __forceinline__ void reset_burst(Lane& L, bool after_ko, const Actors
     L.rec = in;
     L.rec_count++;
   }
-  const uint32_t r = rel_bits(in, (int)L.k);
-  L.f.hist = (r & 1) | ((r & 2) << 15);
-  L.f.hold = (in & IN_ATTACK) ? 1 : 0;
-  const bool stunned = L.f.stun > 0;
-  L.f.stun -= stunned ? 1 : 0;
-  L.f.frame = stunned ? 0 : 1;
+  intro_tick(L.f, in, (int)L.k);
   L.frame_count = -1;
   L.rec_count = 0;
   if constexpr (BOT) {
@@ -1383,6 +1391,7 @@ __device__ __forceinline__ void st_off(T* base, uint32_t byte_off, T v) {
 
 // (REMAP = false: the fast loops' main record, written after the same-step burst -- the action is
 // never DEAD or WIN there, see kLmFast)
+// (restated in packed_record, policy_features, fs_arena1.h obs_move*: deliberate, DESIGN.md "The identity rule")
 template <bool REMAP = true>
 __device__ __forceinline__ void write_obs(const Lane& L, uint8_t* guard, uint8_t* move, float* move_frame,
                                           float* position, int32_t* frame, uint8_t* action, uint8_t* hitstun,
@@ -1627,8 +1636,30 @@ __device__ __forceinline__ void prepare_request(Lane& L, uint32_t in, Pre& pre) 
   pre.q = sT.req_table[sel];
 }
 
-template <int FM, int P2, int WAIT = -1, int TP = kTabLds, bool GEOM = false, bool PK = false, bool PF = false,
-          int LM = kLmGeneric>
+// What a tick is compiled for, by name (row_loop's and step_body's argument; env_step's list: FS_TICK).
+// KIND, where the actions come from: one tick from a row or the host's inputs with the tables in
+// global memory (k_step) | the fused row loop | fused, drawn in-kernel from splitmix64 | fused, P1's
+// sampled from the MLP actor.  OPTS: general geometry (StepParams::geom) | packed trajectory records
+// | each tick's request prepared at the end of the tick before.
+enum StepKind { kOneTick, kRows, kHashed, kPolicy };
+constexpr unsigned kGeom = 1, kPacked = 2, kPrefetch = 4;
+constexpr int kWaitTracked = -1;  // WAIT: the next action is a load the compiler tracks (no settle_w count)
+template <int FM_, int P2_, StepKind KIND_, unsigned OPTS_ = 0, int LM_ = kLmGeneric, int WAIT_ = kWaitTracked>
+struct TickCfg {
+  static constexpr int FM = FM_, P2 = P2_, LM = LM_, WAIT = WAIT_;
+  static constexpr StepKind KIND = KIND_;
+  static constexpr unsigned OPTS = OPTS_;
+  static constexpr bool GEOM = (OPTS & kGeom) != 0, PK = (OPTS & kPacked) != 0, PF = (OPTS & kPrefetch) != 0;
+  static constexpr int TP = KIND == kOneTick ? kTabGlobal : kTabLds;
+  static_assert(!PK || KIND == kRows, "packed trajectories: the fused row loop only");
+  static_assert(!PF || (KIND == kRows && !GEOM && P2 != kActors), "request prefetch: the standard row loop");
+  static_assert(LM == kLmGeneric || KIND == kRows, "launch modes: the fused row loop only");
+};
+// env_step itself keeps a positional list -- declared on the traits type it compiled k_step_n_hashed
+// differently (DESIGN.md "The identity rule") -- which every call site fills by name from a TickCfg:
+#define FS_TICK(C) C::FM, C::P2, C::WAIT, C::TP, C::GEOM, C::PK, C::PF, C::LM
+
+template <int FM, int P2, int WAIT, int TP, bool GEOM, bool PK, bool PF, int LM>
 __device__ __forceinline__ void env_step(Lane& L, uint32_t a_own, const StepParams& p, uint32_t r, uint32_t& next,
                                          const Pre& pre = Pre{}, bool use_pre = false) {
   constexpr bool BOT = P2 == FS_P2_BOT;
@@ -1648,7 +1679,7 @@ __device__ __forceinline__ void env_step(Lane& L, uint32_t a_own, const StepPara
     L.has_term = false;
     L.cum = 0.0;
     if constexpr (G) L.ai = stand_info();  // the burst ends on STAND
-    else L.te = tick_entry_after_burst(L.f);
+    else L.te = tick_entry(L.f);  // (STAND at frame 0 or 1, hitstun surviving: SetupBattleStart keeps it)
     settle_w<WAIT>(next);
     if constexpr (PK) {
       write_packed(L, o.pk_lanes, r, k == 0 ? (uint32_t)L.frame_count : 0u);
@@ -1813,7 +1844,7 @@ __device__ __forceinline__ void env_step(Lane& L, uint32_t a_own, const StepPara
         L.cum = 0.0;
         if constexpr (!FAST) L.has_term = false;
         if constexpr (G) L.ai = stand_info();  // the burst ends on STAND
-        else L.te = tick_entry_after_burst(L.f);
+        else L.te = tick_entry(L.f);  // (STAND at frame 0 or 1, hitstun surviving)
         // (without the pending path around the tick, this branch's join is where the burst's
         // constants would be materialized on every tick: see opaque_burst_results)
         if constexpr (FAST) opaque_burst_results<G, false>(L);
@@ -1871,12 +1902,15 @@ __device__ __forceinline__ void policy_features(const Lane& L, uint32_t& d0, uin
 // flight (read only by its wait), *_rd: the row once resident.  A load is issued every tick (the
 // last rows re-read the last one) so the wait counts hold, and the last one in flight is waited
 // for before the wave ends.
-template <int FM, int P2, bool GEOM, bool PK, bool PF, int LM>
+template <class C>
 __device__ __forceinline__ void row_loop(Lane& L, const StepParams& p, bool reads, const uint8_t* own, uint32_t row_mul,
                                          int a, uint32_t row0, uint32_t row1) {
+  constexpr int P2 = C::P2, LM = C::LM;
+  constexpr bool PK = C::PK, PF = C::PF;
   // (the wait count of settle_w: the vector memory ops every path issues between a row's load
   // and its wait -- one tick's output stores, 10 per-field or 2 packed, plus the next row load)
   constexpr int kRowWait = PK ? 3 : 11;
+  using Tick = TickCfg<C::FM, P2, kRows, C::OPTS, LM, kRowWait>;
   constexpr bool PRIO = LM == kLmFastPrio;
   if constexpr (LM != kLmGeneric) L.f.won = 0;  // (inside I, and nothing in the tick sets it: not carried)
   const int last = p.n_steps - 1;
@@ -1898,8 +1932,7 @@ __device__ __forceinline__ void row_loop(Lane& L, const StepParams& p, bool read
   for (; t < last; t += 2) {
     a_fl = issue(t + 2);
     slice();
-    env_step<FM, P2, kRowWait, kTabLds, GEOM, PK, PF, LM>(L, reads ? a_rd & 7u : 0u, p,
-                                                    (uint32_t)t * row_step + (uint32_t)a, b_fl, pre, have);
+    env_step<FS_TICK(Tick)>(L, reads ? a_rd & 7u : 0u, p, (uint32_t)t * row_step + (uint32_t)a, b_fl, pre, have);
     b_rd = b_fl;
     if constexpr (PF) {
       prepare_request<LM != kLmGeneric>(L, tick_input<P2>(L, reads ? b_rd & 7u : 0u), pre);
@@ -1907,8 +1940,7 @@ __device__ __forceinline__ void row_loop(Lane& L, const StepParams& p, bool read
     }
     b_fl = issue(t + 3);
     slice();
-    env_step<FM, P2, kRowWait, kTabLds, GEOM, PK, PF, LM>(L, reads ? b_rd & 7u : 0u, p,
-                                                    (uint32_t)(t + 1) * row_step + (uint32_t)a, a_fl, pre, PF);
+    env_step<FS_TICK(Tick)>(L, reads ? b_rd & 7u : 0u, p, (uint32_t)(t + 1) * row_step + (uint32_t)a, a_fl, pre, PF);
     a_rd = a_fl;
     if constexpr (PF) {
       if (t + 2 <= last) prepare_request<LM != kLmGeneric>(L, tick_input<P2>(L, reads ? a_rd & 7u : 0u), pre);
@@ -1917,8 +1949,7 @@ __device__ __forceinline__ void row_loop(Lane& L, const StepParams& p, bool read
   if (t == last) {  // an odd tick count: the last tick waits for a re-read of the last row
     a_fl = issue(t + 2);
     uint32_t b_last = b_fl;  // (b_fl itself stays the in-flight value for the final wait)
-    env_step<FM, P2, kRowWait, kTabLds, GEOM, PK, PF, LM>(L, reads ? a_rd & 7u : 0u, p,
-                                                    (uint32_t)t * row_step + (uint32_t)a, b_last, pre, have);
+    env_step<FS_TICK(Tick)>(L, reads ? a_rd & 7u : 0u, p, (uint32_t)t * row_step + (uint32_t)a, b_last, pre, have);
   }
   asm volatile("s_waitcnt vmcnt(0)" ::"v"(a_fl), "v"(b_fl) : "memory");  // no load outlives the wave
   if constexpr (LM != kLmGeneric) L.pending = L.has_term = 0;  // (what every same-step tick leaves; n_steps > 0)
@@ -1926,14 +1957,15 @@ __device__ __forceinline__ void row_loop(Lane& L, const StepParams& p, bool read
 
 // One fused launch over all arenas (k_step_n*, the rollout: state stays in registers between the
 // p.n_steps ticks); the one-tick launch is step_one below.
-// HASH draws the actions in-kernel from splitmix64 instead of reading action rows.
-// POL samples P1's action every tick from the MLP actor (fs_policy.h); its MFMAs and lane
+// HASH (kHashed) draws the actions in-kernel from splitmix64 instead of reading action rows.
+// POL (kPolicy) samples P1's action every tick from the MLP actor (fs_policy.h); its MFMAs and lane
 // exchanges need the whole wave, so lanes past the last arena stay in the loop (on a copy
 // of arena 0 that they never store) unless their whole wave is idle.
-template <int FM, int P2, bool FUSED, bool HASH, bool POL = false, bool GEOM = false, bool PK = false, bool PF = false>
+template <class C>
 __device__ __forceinline__ void step_body(const StepParams& p) {
-  static_assert(!PK || (FUSED && !HASH && !POL), "packed trajectories: the fused row loop only");
-  static_assert(!PF || (FUSED && !HASH && !POL && !GEOM && P2 != kActors), "request prefetch: the standard row loop");
+  static_assert(C::KIND != kOneTick && C::LM == kLmGeneric && C::WAIT == kWaitTracked, "a fused launch's options");
+  constexpr int FM = C::FM, P2 = C::P2;
+  constexpr bool HASH = C::KIND == kHashed, POL = C::KIND == kPolicy, GEOM = C::GEOM, PF = C::PF;
   const int l = blockIdx.x * blockDim.x + threadIdx.x;
   const bool active = l < 2 * p.n_envs;
   const int a = active ? l >> 1 : 0;
@@ -1967,14 +1999,14 @@ __device__ __forceinline__ void step_body(const StepParams& p) {
   const uint32_t row_mul = reads ? (uint32_t)p.n_envs : 0u;
   auto issue = [&](int t) -> uint32_t { return row_load(own + (uint32_t)min(t, last) * row_mul + (uint32_t)a); };
   uint32_t next, row1 = 0;
-  if constexpr (FUSED && !HASH && !POL) {
+  if constexpr (C::KIND == kRows) {
     next = issue(0);
     row1 = issue(1);
   } else {
     next = fetch(0);
   }
   if constexpr (POL) stage_policy(p.pol);
-  if constexpr (FUSED) stage_tables<P2 == FS_P2_BOT || P2 == kActors>();
+  stage_tables<P2 == FS_P2_BOT || P2 == kActors>();
   if constexpr (POL) {
     if ((l & ~63) >= 2 * p.n_envs) return;  // the whole wave is past the last arena
   } else {
@@ -1999,42 +2031,41 @@ __device__ __forceinline__ void step_body(const StepParams& p) {
           if (p.pol.actions) p.pol.actions[row] = (uint8_t)po.action;
           if (p.pol.logp) p.pol.logp[row] = po.logp;
         }
-        env_step<FM, P2, -1, kTabLds, GEOM>(L, k == 0 ? po.action : act & 7u, p, (uint32_t)t * row_step + (uint32_t)a,
-                                            next);
+        env_step<FS_TICK(C)>(L, k == 0 ? po.action : act & 7u, p, (uint32_t)t * row_step + (uint32_t)a, next);
       }
       policy_features(L, d0, d1);
     }
-  } else if constexpr (FUSED) {
+  } else if constexpr (HASH) {
     const uint32_t row_step = (uint32_t)p.out_stride_steps * (uint32_t)p.n_envs;
-    if constexpr (HASH) {
-      const uint32_t grp = prio_group();
-      for (int t = 0; t < p.n_steps; t++) {
-        const uint32_t act = next;
-        next = fetch(min(t + 1, p.n_steps - 1));
-        if (p.prio) prio_slice(grp);
-        env_step<FM, P2, -1, kTabLds, GEOM>(L, act & 7u, p, (uint32_t)t * row_step + (uint32_t)a, next);
-      }
-    } else {
-      // the row loop, compiled once per launch mode (kLmFast); the choice is per wave -- no barrier
-      // follows the table staging, so the waves of a block may run different loops
-      // (rows 0 and 1 made resident here, ahead of the choice: no load is in flight where the loops
-      // part and meet)
-      uint32_t row0, row1_rd;  // (early-clobber outputs: the loads' registers die here)
-      asm volatile("s_waitcnt vmcnt(0)\n\tv_mov_b32 %0, %2\n\tv_mov_b32 %1, %3" : "=&v"(row0), "=&v"(row1_rd)
-                   : "v"(next), "v"(row1) : "memory");
-      const bool fast = p.autoreset_mode == FS_AUTORESET_SAME_STEP && p.dense_reward &&
-                        __builtin_amdgcn_ballot_w64((L.pending != 0) | !in_fast_set(L.f)) == 0;
-      // (the generic loop only: general geometry and the per-arena actors, off the throughput path,
-      // and the scripted bot, whose tick has no registers to spare for a second loop's allocation)
-      if constexpr (GEOM || P2 == kActors || P2 == FS_P2_BOT) {
-        row_loop<FM, P2, GEOM, PK, PF, kLmGeneric>(L, p, reads, own, row_mul, a, row0, row1_rd);
-      } else if constexpr (PF) {  // (one wave per SIMD: no slices unless forced)
-        if (fast && !p.prio) row_loop<FM, P2, GEOM, PK, PF, kLmFast>(L, p, reads, own, row_mul, a, row0, row1_rd);
-        else row_loop<FM, P2, GEOM, PK, PF, kLmGeneric>(L, p, reads, own, row_mul, a, row0, row1_rd);
-      } else {  // (without slices these launches are one-tick ones, or forced: the generic loop)
-        if (fast && p.prio) row_loop<FM, P2, GEOM, PK, PF, kLmFastPrio>(L, p, reads, own, row_mul, a, row0, row1_rd);
-        else row_loop<FM, P2, GEOM, PK, PF, kLmGeneric>(L, p, reads, own, row_mul, a, row0, row1_rd);
-      }
+    const uint32_t grp = prio_group();
+    for (int t = 0; t < p.n_steps; t++) {
+      const uint32_t act = next;
+      next = fetch(min(t + 1, p.n_steps - 1));
+      if (p.prio) prio_slice(grp);
+      env_step<FS_TICK(C)>(L, act & 7u, p, (uint32_t)t * row_step + (uint32_t)a, next);
+    }
+  } else {
+    // the row loop, compiled once per launch mode (kLmFast); the choice is per wave -- no barrier
+    // follows the table staging, so the waves of a block may run different loops
+    // (rows 0 and 1 made resident here, ahead of the choice: no load is in flight where the loops
+    // part and meet)
+    uint32_t row0, row1_rd;  // (early-clobber outputs: the loads' registers die here)
+    asm volatile("s_waitcnt vmcnt(0)\n\tv_mov_b32 %0, %2\n\tv_mov_b32 %1, %3" : "=&v"(row0), "=&v"(row1_rd)
+                 : "v"(next), "v"(row1) : "memory");
+    const bool fast = p.autoreset_mode == FS_AUTORESET_SAME_STEP && p.dense_reward &&
+                      __builtin_amdgcn_ballot_w64((L.pending != 0) | !in_fast_set(L.f)) == 0;
+    using Fast = TickCfg<FM, P2, kRows, C::OPTS, kLmFast>;
+    using FastPrio = TickCfg<FM, P2, kRows, C::OPTS, kLmFastPrio>;
+    // (the generic loop only: general geometry and the per-arena actors, off the throughput path,
+    // and the scripted bot, whose tick has no registers to spare for a second loop's allocation)
+    if constexpr (GEOM || P2 == kActors || P2 == FS_P2_BOT) {
+      row_loop<C>(L, p, reads, own, row_mul, a, row0, row1_rd);
+    } else if constexpr (PF) {  // (one wave per SIMD: no slices unless forced)
+      if (fast && !p.prio) row_loop<Fast>(L, p, reads, own, row_mul, a, row0, row1_rd);
+      else row_loop<C>(L, p, reads, own, row_mul, a, row0, row1_rd);
+    } else {  // (without slices these launches are one-tick ones, or forced: the generic loop)
+      if (fast && p.prio) row_loop<FastPrio>(L, p, reads, own, row_mul, a, row0, row1_rd);
+      else row_loop<C>(L, p, reads, own, row_mul, a, row0, row1_rd);
     }
   }
   if (active) {
@@ -2102,11 +2133,13 @@ __device__ __forceinline__ void step_one(const StepParams& p) {
   if (geom) {  // (general geometry: position.y, read after the branch; off the common path)
     float* py = reinterpret_cast<float*>(p.st.posy) + 2 * a + (int)k;
     L.f.y = *py;
-    env_step<FM, P2, -1, kTabGlobal, true>(L, in & 7u, p, (uint32_t)a, none);
+    using Geom = TickCfg<FM, P2, kOneTick, kGeom>;
+    env_step<FS_TICK(Geom)>(L, in & 7u, p, (uint32_t)a, none);
     store_lane<P2>(L, p.st, a);
     *py = L.f.y;
   } else {
-    env_step<FM, P2, -1, kTabGlobal>(L, in & 7u, p, (uint32_t)a, none);
+    using Std = TickCfg<FM, P2, kOneTick>;
+    env_step<FS_TICK(Std)>(L, in & 7u, p, (uint32_t)a, none);
     store_lane<P2>(L, p.st, a);
   }
 }
@@ -2120,15 +2153,15 @@ __global__ __launch_bounds__(256) void k_step(StepParams p) {
 // uniform over the launch) as two loops: the standard loop carries none of the y state.
 template <int FM, int P2>
 __global__ __launch_bounds__(256) void k_step_n(StepParams p) {
-  if (p.geom) step_body<FM, P2, true, false, false, true>(p);
-  else step_body<FM, P2, true, false>(p);
+  if (p.geom) step_body<TickCfg<FM, P2, kRows, kGeom>>(p);
+  else step_body<TickCfg<FM, P2, kRows>>(p);
 }
 
 // fs_step_n_packed: the row loop of k_step_n storing packed trajectory records
 template <int FM, int P2>
 __global__ __launch_bounds__(256) void k_step_n_packed(StepParams p) {
-  if (p.geom) step_body<FM, P2, true, false, false, true, true>(p);
-  else step_body<FM, P2, true, false, false, false, true>(p);
+  if (p.geom) step_body<TickCfg<FM, P2, kRows, kGeom | kPacked>>(p);
+  else step_body<TickCfg<FM, P2, kRows, kPacked>>(p);
 }
 
 // The same row loops with each tick's request prepared at the end of the tick before
@@ -2137,23 +2170,23 @@ __global__ __launch_bounds__(256) void k_step_n_packed(StepParams p) {
 // occupancy too (132 VGPRs instead of 122: three waves per SIMD instead of four).
 template <int FM, int P2>
 __global__ __launch_bounds__(256) void k_step_n_pf(StepParams p) {
-  step_body<FM, P2, true, false, false, false, false, true>(p);
+  step_body<TickCfg<FM, P2, kRows, kPrefetch>>(p);
 }
 template <int FM, int P2>
 __global__ __launch_bounds__(256) void k_step_n_packed_pf(StepParams p) {
-  step_body<FM, P2, true, false, false, false, true, true>(p);
+  step_body<TickCfg<FM, P2, kRows, kPacked | kPrefetch>>(p);
 }
 
 template <int FM, int P2>
 __global__ __launch_bounds__(256) void k_step_n_hashed(StepParams p) {
-  if (p.geom) step_body<FM, P2, true, true, false, true>(p);
-  else step_body<FM, P2, true, true>(p);
+  if (p.geom) step_body<TickCfg<FM, P2, kHashed, kGeom>>(p);
+  else step_body<TickCfg<FM, P2, kHashed>>(p);
 }
 
 template <int FM, int P2>
 __global__ __launch_bounds__(256) void k_step_n_policy(StepParams p) {
-  if (p.geom) step_body<FM, P2, true, false, true, true>(p);
-  else step_body<FM, P2, true, false, true>(p);
+  if (p.geom) step_body<TickCfg<FM, P2, kPolicy, kGeom>>(p);
+  else step_body<TickCfg<FM, P2, kPolicy>>(p);
 }
 
 // FootsiesEnv.reset (FE:482-515) / RESET (BC:143-146) / game start (BC:105-128), every handle
@@ -2292,13 +2325,13 @@ __global__ __launch_bounds__(256) void k_get_state(DevState st, fs_arena_state* 
       g.position_y = f.y;
     }
     s.frame_count = A.frame_count;
-    s.recording_count = (int32_t)A.rec_count;
-    s.recording_last[0] = (uint8_t)A.rec1;
-    s.recording_last[1] = (uint8_t)A.rec2;
-    s.actor_input[0] = (uint8_t)A.act1;
-    s.actor_input[1] = (uint8_t)A.act2;
-    s.reset_pending = A.pending;
-    s.has_terminated = A.has_term;
+    s.recording_count = (int32_t)A.h.rec_count;
+    s.recording_last[0] = (uint8_t)A.h.rec[0];
+    s.recording_last[1] = (uint8_t)A.h.rec[1];
+    s.actor_input[0] = (uint8_t)A.h.act[0];
+    s.actor_input[1] = (uint8_t)A.h.act[1];
+    s.reset_pending = (uint8_t)A.h.pending;
+    s.has_terminated = (uint8_t)A.h.has_term;
     s.pad0[0] = s.pad0[1] = 0;
     s.cumulative_reward = A.cum;
     s.rng[0] = A.rng.x;
@@ -2312,7 +2345,7 @@ __global__ __launch_bounds__(256) void k_get_state(DevState st, fs_arena_state* 
     s.attack_index = b2.attack_index;
     s.prev_distance = b2.prev_distance;
     s.prev_opponent_action = b2.prev_opponent_action;
-    s.p2_bot = A.p2bot;
+    s.p2_bot = (uint8_t)A.h.p2bot;
     s.bot_ready[0] = b1.ready;
     s.bot_ready[1] = b2.ready;
     s.bot_input[0] = b1.input;
@@ -2339,8 +2372,8 @@ __global__ __launch_bounds__(256) void k_get_state(DevState st, fs_arena_state* 
     e.p1Position = A.f0.x;
     e.p2Position = A.f1.x;
     e.globalFrame = A.frame_count;
-    e.p1MostRecentAction = A.rec_count > 0 ? (int32_t)A.rec1 : 0;
-    e.p2MostRecentAction = A.rec_count > 0 ? (int32_t)A.rec2 : 0;
+    e.p1MostRecentAction = A.h.rec_count > 0 ? (int32_t)A.h.rec[0] : 0;
+    e.p2MostRecentAction = A.h.rec_count > 0 ? (int32_t)A.h.rec[1] : 0;
     e.p1Hitstun = A.f0.stun;
     e.p2Hitstun = A.f1.stun;
     env[i] = e;
@@ -2392,16 +2425,16 @@ __global__ __launch_bounds__(256) void k_set_state(DevState st, const fs_arena_s
     f.won = g.has_won;
   }
   A.frame_count = s.frame_count;
-  A.rec_count = (uint32_t)s.recording_count;
-  A.rec1 = s.recording_last[0] & 7;
-  A.rec2 = s.recording_last[1] & 7;
-  A.act1 = s.actor_input[0] & 7;
-  A.act2 = s.actor_input[1] & 7;
-  A.pending = s.reset_pending;
-  A.has_term = s.has_terminated;
+  A.h.rec_count = (uint32_t)s.recording_count;
+  A.h.rec[0] = s.recording_last[0] & 7;
+  A.h.rec[1] = s.recording_last[1] & 7;
+  A.h.act[0] = s.actor_input[0] & 7;
+  A.h.act[1] = s.actor_input[1] & 7;
+  A.h.pending = s.reset_pending != 0;
+  A.h.has_term = s.has_terminated != 0;
   A.cum = s.cumulative_reward;
   A.rng = make_uint4(s.rng[0], s.rng[1], s.rng[2], s.rng[3]);
-  A.p2bot = s.p2_bot != 0;
+  A.h.p2bot = s.p2_bot != 0;
   A.bw[1] = bot_import(s.move_plan, s.move_index, s.attack_plan, s.attack_index, s.prev_distance,
                        s.prev_opponent_action, s.bot_ready[1], s.bot_input[1]);
   A.bw[0] = bot_import(s.p1_move_plan, s.p1_move_index, s.p1_attack_plan, s.p1_attack_index, s.p1_prev_distance,
@@ -2416,18 +2449,13 @@ __global__ __launch_bounds__(256) void k_set_state(DevState st, const fs_arena_s
 // ---------------------------------------------------------------------------
 static inline dim3 grid_for(int n) { return dim3((unsigned)((n + kBlock - 1) / kBlock)); }
 
-// Which kernel runs a fused launch with action rows.  The two-lane kernel needs two waves per SIMD
-// to hide its LDS round trips, and has them from 32 768 arenas on; the one-lane kernel issues ~18 %
-// fewer instructions per arena-tick but needs twice the arenas for the same waves: with one wave
-// per SIMD (65 536 arenas, C3) it exposes the tick's dependent LDS reads and runs 16-18 % slower;
-// from two waves per SIMD (131 072 arenas) on it matches the two-lane kernel with a remote P2 and
-// beats it by 12-25 % with the scripted bot.  So the one-lane kernel takes the
-// launches with at least two of its waves per SIMD -- except packed launches with a remote P2 from
-// four of them on (262 144 arenas), where the two-lane packed kernel at 4 resident waves per SIMD is
-// ahead (+4.3 % at 262 144, +1.4 % at 524 288; 131 072: one lane +2.1 %; profiles/r05l_ab_lanes_*.txt,
-// r05m_ab_lanes_524288.txt); the per-field two-lane kernel, with its eight stores per tick, is not
-// (7.2e10 vs 7.8-7.9e10 at 262 144).
-// FOOTSIES_FUSED_LANES=1 / 2 forces one kernel (A/B timing, and the parity suite runs both).
+// A FOOTSIES_* switch of the launch choice (A/B timing, and the parity suite runs both sides): 1 / 2
+// when the variable starts with the digit `first` / the one after it, else 0 (not forced).
+static int env_switch(const char* name, char first) {
+  const char* e = getenv(name);
+  return e && (e[0] == first || e[0] == first + 1) ? e[0] - first + 1 : 0;
+}
+
 static int simd_count() {
   int dev = 0, cus = 0;
   if (hipGetDevice(&dev) != hipSuccess ||
@@ -2435,96 +2463,86 @@ static int simd_count() {
     cus = 256;  // MI355X
   return 4 * cus;
 }
-static bool fused_one_lane(int n_envs, int variant, bool packed) {
-  static const int forced = [] {
-    const char* e = getenv("FOOTSIES_FUSED_LANES");
-    return e && (e[0] == '1' || e[0] == '2') ? e[0] - '0' : 0;
-  }();
-  if (forced) return forced == 1;
-  static const int64_t threshold = 2 * 64 * (int64_t)simd_count();
-  if (packed && variant == FS_P2_EXTERNAL) return n_envs >= threshold && n_envs < 2 * threshold;
-  return n_envs >= threshold;
-}
 
-// Whether a fused launch with `lanes` lanes (two per arena, or one for the one-lane kernel) holds
-// more than one wave per SIMD, the case prio_slice is for.  FOOTSIES_PRIO=0 / 1 forces it off / on
-// (A/B timing).
-static int prio_forced() {  // 0: not forced, 1: off, 2: on
-  static const int forced = [] {
-    const char* e = getenv("FOOTSIES_PRIO");
-    return e && (e[0] == '0' || e[0] == '1') ? e[0] - '0' + 1 : 0;
-  }();
-  return forced;
-}
-static bool waves_above_simds(int64_t lanes) {
-  if (prio_forced()) return prio_forced() == 2;
-  static const int simds = simd_count();
-  return (lanes + 63) / 64 > simds;
-}
-static bool two_waves_per_simd(int n_envs) { return waves_above_simds(2 * (int64_t)n_envs); }
-// The one-lane kernels: the slicing pays at two waves per SIMD (131 072 arenas: +4.4 % / +4.9 % remote
-// P2, +4.1 % / +7.1 % bot, per-field / packed) and costs the remote-P2 case at four (262 144: -2.3 %,
-// bot +3.3 %; profiles/r05g_ab_onelane_prio_131k.txt, r05h_ab_onelane_prio_*.txt), so only there.
-static bool one_lane_prio(int n_envs) {
-  if (prio_forced()) return prio_forced() == 2;
-  static const int simds = simd_count();
-  const int64_t waves = ((int64_t)n_envs + 63) / 64;
-  return waves > simds && waves <= 2 * (int64_t)simds;
-}
-
-// Whether a two-lane fused row launch prepares each tick's request at the end of the tick before
-// (Pre / prepare_request): at one wave per SIMD, where no partner wave issues in that LDS wait
-// (DESIGN.md section 5); same-step auto-reset only (no tick is a next-step reset burst).
-// FOOTSIES_PREFETCH=0 / 1 forces it off / on (A/B timing, and the parity suite runs both).
-// (row_launch: a fused launch over action rows -- not the in-kernel actor's, not hashed actions)
-static bool request_prefetch(bool row_launch, int autoreset_mode, bool geom, int n_steps, int n_envs) {
-  static const int forced = [] {
-    const char* e = getenv("FOOTSIES_PREFETCH");
-    return e && (e[0] == '0' || e[0] == '1') ? e[0] - '0' + 1 : 0;
-  }();
-  if (!row_launch || autoreset_mode != FS_AUTORESET_SAME_STEP || geom || n_steps < 2) return false;
-  if (forced) return forced == 2;
-  return !two_waves_per_simd(n_envs);
+// Which kernel runs a step launch and with which launcher-set parameters, for launch_step_p2 (which
+// launches it) and step_kernel_name (which names it); launch_choice's returns are in order of precedence.
+enum StepKernel {
+  kKStep, kKStepN, kKStepNPf, kKStepNPacked, kKStepNPackedPf, kKStepN1, kKStepN1Packed, kKStepNHashed, kKStepNPolicy
+};
+static const char* const kStepKernelName[] = {"k_step",          "k_step_n",  "k_step_n_pf",      "k_step_n_packed",
+                                              "k_step_n_packed_pf", "k_step_n1", "k_step_n1_packed", "k_step_n_hashed",
+                                              "k_step_n_policy"};
+struct LaunchChoice {
+  StepKernel kernel;
+  bool prio, prefetch;  // StepParams::prio / prefetch
+  int lanes;            // per arena
+};
+// (rows: the launch reads action rows, not hashed actions; a packed launch always does: fs_api checks)
+static LaunchChoice launch_choice(bool policy, bool rows, int n_steps, int n_envs, int variant, bool geom, bool packed,
+                                  int autoreset_mode) {
+  static const int lanes_forced = env_switch("FOOTSIES_FUSED_LANES", '1');  // 1 / 2: that many lanes per arena
+  static const int prio_forced = env_switch("FOOTSIES_PRIO", '0');          // 1: off, 2: on
+  static const int prefetch_forced = env_switch("FOOTSIES_PREFETCH", '0');  // 1: off, 2: on
+  static const int64_t simds = simd_count();
+  const int64_t waves1 = ((int64_t)n_envs + 63) / 64, waves2 = (2 * (int64_t)n_envs + 63) / 64;  // one / two lanes
+  const bool row_launch = !policy && rows;  // a fused launch over action rows, or one tick
+  // Time-sliced priority (prio_slice) is for a grid with more than one wave per SIMD.
+  const bool prio = prio_forced ? prio_forced == 2 : waves2 > simds;
+  // The one-lane kernel.  The two-lane kernel needs two waves per SIMD to hide its LDS round trips,
+  // and has them from 32 768 arenas on; the one-lane kernel issues ~18 % fewer instructions per
+  // arena-tick but needs twice the arenas for the same waves: with one wave per SIMD (65 536 arenas,
+  // C3) it exposes the tick's dependent LDS reads and runs 16-18 % slower; from two waves per SIMD
+  // (131 072 arenas) on it matches the two-lane kernel with a remote P2 and beats it by 12-25 % with
+  // the scripted bot.  So it takes the launches with at least two of its waves
+  // per SIMD -- except packed launches with a remote P2 from four of them on (262 144 arenas), where
+  // the two-lane packed kernel at 4 resident waves per SIMD is ahead (+4.3 % at 262 144, +1.4 % at
+  // 524 288; 131 072: one lane +2.1 %; profiles/r05l_ab_lanes_*.txt, r05m_ab_lanes_524288.txt); the
+  // per-field two-lane kernel, with its eight stores per tick, is not (7.2e10 vs 7.8-7.9e10 at
+  // 262 144).  It has no general-geometry tick and no per-arena actors.
+  const int64_t from = 2 * 64 * simds;
+  const bool one_lane = row_launch && variant != kActors && !geom &&
+                        (lanes_forced ? lanes_forced == 1
+                                      : n_envs >= from && !(packed && variant == FS_P2_EXTERNAL && n_envs >= 2 * from));
+  // Its slicing pays at two waves per SIMD (131 072 arenas: +4.4 % / +4.9 % remote P2, +4.1 % / +7.1 %
+  // bot, per-field / packed) and costs the remote-P2 case at four (262 144: -2.3 %, bot +3.3 %;
+  // profiles/r05g_ab_onelane_prio_131k.txt, r05h_ab_onelane_prio_*.txt), so only there.
+  const bool prio1 = prio_forced ? prio_forced == 2 : waves1 > simds && waves1 <= 2 * simds;
+  // The request prefetch (Pre / prepare_request) of the two-lane row loop: at one wave per SIMD, where
+  // no partner wave issues in that LDS wait; same-step auto-reset only (no tick
+  // is a next-step reset burst), the standard tick only, never the per-arena actors.
+  const bool prefetch = !one_lane && row_launch && variant != kActors && !geom && n_steps >= 2 &&
+                        autoreset_mode == FS_AUTORESET_SAME_STEP && (prefetch_forced ? prefetch_forced == 2 : !prio);
+  if (policy) return {kKStepNPolicy, prio, false, 2};
+  if (packed && one_lane) return {kKStepN1Packed, prio1, false, 1};
+  if (packed) return {prefetch ? kKStepNPackedPf : kKStepNPacked, prio, prefetch, 2};
+  if (!rows) return {kKStepNHashed, prio, false, 2};
+  if (n_steps == 1) return {kKStep, prio, false, 2};
+  if (one_lane) return {kKStepN1, prio1, false, 1};
+  return {prefetch ? kKStepNPf : kKStepN, prio, prefetch, 2};
 }
 
 template <int FM, int P2>
 static void launch_step_p2(const StepParams& p_in, hipStream_t s) {
-  const dim3 grid = grid_for(2 * p_in.n_envs), block(kBlock);
+  const LaunchChoice c = launch_choice(p_in.pol.w1 != nullptr, p_in.p1 != nullptr, p_in.n_steps, p_in.n_envs, P2,
+                                       p_in.geom != 0, p_in.out.pk_lanes != nullptr, p_in.autoreset_mode);
+  const dim3 grid = grid_for(c.lanes * p_in.n_envs), block(kBlock);
   StepParams p = p_in;
-  p.prio = two_waves_per_simd(p.n_envs);
-  p.prefetch = P2 != kActors && request_prefetch(!p.pol.w1 && p.p1, p.autoreset_mode, p.geom, p.n_steps, p.n_envs);
-  if (p.pol.w1) hipLaunchKernelGGL((k_step_n_policy<FM, P2>), grid, block, 0, s, p);
-  else if (p.out.pk_lanes) {  // (rows: fs_api checks)
-    if constexpr (P2 != kActors) {
-      if (!p.geom && fused_one_lane(p.n_envs, P2, true)) {
-        p.prio = one_lane_prio(p.n_envs);
-        hipLaunchKernelGGL((k_step_n1_packed<FM, P2>), grid_for(p.n_envs), block, 0, s, p);
-        return;
-      }
-    }
-    if constexpr (P2 != kActors) {
-      if (p.prefetch) {
-        hipLaunchKernelGGL((k_step_n_packed_pf<FM, P2>), grid, block, 0, s, p);
-        return;
-      }
-    }
-    hipLaunchKernelGGL((k_step_n_packed<FM, P2>), grid, block, 0, s, p);
+  p.prio = c.prio;
+  p.prefetch = c.prefetch;
+  constexpr bool kStd = P2 != kActors;  // (the one-lane and prefetch kernels are not built for kActors)
+#define FS_LAUNCH(K) hipLaunchKernelGGL((K<FM, P2>), grid, block, 0, s, p)
+  switch (c.kernel) {  // (cases in launch_choice's order: the device code numbers the kernels by it)
+    case kKStepNPolicy: FS_LAUNCH(k_step_n_policy); break;
+    case kKStepN1Packed: if constexpr (kStd) FS_LAUNCH(k_step_n1_packed); break;
+    case kKStepNPackedPf: if constexpr (kStd) FS_LAUNCH(k_step_n_packed_pf); break;
+    case kKStepNPacked: FS_LAUNCH(k_step_n_packed); break;
+    case kKStepNHashed: FS_LAUNCH(k_step_n_hashed); break;
+    case kKStep: FS_LAUNCH(k_step); break;
+    case kKStepN1: if constexpr (kStd) FS_LAUNCH(k_step_n1); break;
+    case kKStepNPf: if constexpr (kStd) FS_LAUNCH(k_step_n_pf); break;
+    case kKStepN: FS_LAUNCH(k_step_n); break;
   }
-  else if (!p.p1) hipLaunchKernelGGL((k_step_n_hashed<FM, P2>), grid, block, 0, s, p);
-  else if (p.n_steps == 1) hipLaunchKernelGGL((k_step<FM, P2>), grid, block, 0, s, p);
-  else if constexpr (P2 != kActors) {
-    // (the one-lane kernel has no general-geometry tick: a geom launch takes the two-lane one)
-    if (!p.geom && fused_one_lane(p.n_envs, P2, false)) {
-      p.prio = one_lane_prio(p.n_envs);
-      hipLaunchKernelGGL((k_step_n1<FM, P2>), grid_for(p.n_envs), block, 0, s, p);
-    } else if (p.prefetch) {
-      hipLaunchKernelGGL((k_step_n_pf<FM, P2>), grid, block, 0, s, p);
-    } else {
-      hipLaunchKernelGGL((k_step_n<FM, P2>), grid, block, 0, s, p);
-    }
-  } else {
-    hipLaunchKernelGGL((k_step_n<FM, P2>), grid, block, 0, s, p);
-  }
+#undef FS_LAUNCH
 }
 
 template <int FM>
@@ -2547,11 +2565,8 @@ hipError_t launch_step(const StepParams& p, int float_mode, int variant, hipStre
 const char* step_kernel_name(bool policy, bool hashed, int n_steps, int n_envs, int float_mode, int variant, bool geom,
                              bool packed, int autoreset_mode) {
   static thread_local char buf[64];
-  const bool one = !policy && !hashed && variant != kActors && !geom && fused_one_lane(n_envs, variant, packed);
-  const bool pf = !one && variant != kActors && request_prefetch(!policy && !hashed, autoreset_mode, geom, n_steps, n_envs);
-  const char* k = policy ? "k_step_n_policy" : packed ? (one ? "k_step_n1_packed" : pf ? "k_step_n_packed_pf" : "k_step_n_packed")
-                : hashed ? "k_step_n_hashed" : n_steps == 1 ? "k_step" : one ? "k_step_n1" : pf ? "k_step_n_pf" : "k_step_n";
-  snprintf(buf, sizeof buf, "fsk::%s<%d, %d>", k, float_mode == FS_FLOAT_DOUBLE ? 1 : 0, variant);
+  const LaunchChoice c = launch_choice(policy, !hashed, n_steps, n_envs, variant, geom, packed, autoreset_mode);
+  snprintf(buf, sizeof buf, "fsk::%s<%d, %d>", kStepKernelName[c.kernel], float_mode == FS_FLOAT_DOUBLE, variant);
   return buf;
 }
 

@@ -870,3 +870,63 @@ def test_step_kernel_names_the_launched_kernel():
             assert name(huge, 1000, 4) == want, p2
             assert name(huge, 1000) == "fsk::k_step_n1<0, %d>" % (p2 == "bot"), p2
         huge.close()
+
+
+# What step_kernel_name answers at 64 arenas (far below one wave per SIMD) with a remote P2, same-step
+# auto-reset, under each launch switch -- written down from the launcher's rules, not read from it:
+# the switches are FOOTSIES_PREFETCH / FOOTSIES_PRIO = 0 / 1 (off / on) and FOOTSIES_FUSED_LANES = 1 / 2;
+# unforced, a grid this small takes the two-lane kernel with the request prefetch and no slices;
+# the prefetch needs two ticks, and is off wherever the slices are on; one per-field tick is k_step.
+# (per-field 4 ticks, packed 4 ticks, per-field 1 tick, packed 1 tick)
+SWITCH_KERNELS = {
+    "FOOTSIES_PREFETCH=0": ("k_step_n", "k_step_n_packed", "k_step", "k_step_n_packed"),
+    "FOOTSIES_PREFETCH=1": ("k_step_n_pf", "k_step_n_packed_pf", "k_step", "k_step_n_packed"),
+    "FOOTSIES_PRIO=0": ("k_step_n_pf", "k_step_n_packed_pf", "k_step", "k_step_n_packed"),
+    "FOOTSIES_PRIO=1": ("k_step_n", "k_step_n_packed", "k_step", "k_step_n_packed"),
+    "FOOTSIES_FUSED_LANES=1": ("k_step_n1", "k_step_n1_packed", "k_step", "k_step_n1_packed"),
+    "FOOTSIES_FUSED_LANES=2": ("k_step_n_pf", "k_step_n_packed_pf", "k_step", "k_step_n_packed"),
+}
+SWITCH_CASE = "FOOTSIES_SWITCH_CASE"  # set in the child process that runs one of them
+
+
+def test_launch_switches_name_and_run_the_same_kernels(oracle_lib):
+    """Each launch switch in a fresh process (they are read once per process): fs_step_kernel gives the
+    names above, the in-kernel-actor, hashed and per-arena-actor launches keep their kernels whatever
+    is forced, and a per-field and a packed launch of 4 ticks match the oracle bit for bit."""
+    import os
+    import subprocess
+    import sys
+    case = os.environ.get(SWITCH_CASE)
+    if case is None:  # the parent: the six children side by side
+        root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+        base = {k: v for k, v in os.environ.items() if k.split("=")[0] not in {c.split("=")[0] for c in SWITCH_KERNELS}}
+        cmd = [sys.executable, "-m", "pytest", "-x", "-q", "-m", "gpu", "-p", "no:cacheprovider",
+               os.path.abspath(__file__) + "::test_launch_switches_name_and_run_the_same_kernels"]
+        kids = {c: subprocess.Popen(cmd, cwd=root, env=dict(base, **dict([c.split("=")]), **{SWITCH_CASE: c}),
+                                    stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True) for c in SWITCH_KERNELS}
+        for c, kid in kids.items():
+            out = kid.communicate(timeout=300)[0]
+            assert kid.returncode == 0 and "1 passed" in out, c + "\n" + out[-3000:]
+        return
+    from footsies_gym_amd._lib import lib
+    from footsies_gym_amd.simulator import FootsiesSim
+    from tests.parity_utils import random_states
+    from tests.test_gpu_launch_modes import launch_vs_oracle, oracle_run, rows_for
+    assert os.environ[case.split("=")[0]] == case.split("=")[1]
+    n, ticks = 64, 4
+    want = ["fsk::%s<0, 0>" % k for k in SWITCH_KERNELS[case]]
+    sim = FootsiesSim(n, p2_mode="external")
+    name = lambda t, fl=0: lib().fs_step_kernel(sim.handle, t, fl).decode()  # noqa: E731
+    got = [name(ticks), name(ticks, _abi.FS_KERNEL_PACKED), name(1), name(1, _abi.FS_KERNEL_PACKED)]
+    assert got == want
+    assert name(ticks, _abi.FS_KERNEL_HASHED) == "fsk::k_step_n_hashed<0, 0>"
+    assert name(ticks, _abi.FS_KERNEL_POLICY) == "fsk::k_step_n_policy<0, 0>"
+    sim.set_p2_mode("bot", np.arange(n) % 2 == 0)  # per-arena actors: never one-lane, never prefetched
+    assert name(ticks) == "fsk::k_step_n<0, 3>" and name(ticks, _abi.FS_KERNEL_PACKED) == "fsk::k_step_n_packed<0, 3>"
+    sim.close()
+    st = random_states(n, np.random.default_rng(21))
+    st["reset_pending"] = 0
+    h1, h2 = rows_for(n, ticks, 0xB1, "external")
+    ref = oracle_run(oracle_lib, ("switches",), st, h1, h2, "external", "same_step")
+    for packed in (False, True):
+        launch_vs_oracle(ref, "external", "same_step", ticks, packed, kernel=want[packed])

@@ -57,7 +57,6 @@ PHASES = {
     "push_character_vs_character": "UpdatePushCharacterVsCharacter (BC:483-501)",
     "push_character_vs_background": "UpdatePushCharacterVsBackground (BC:503-519)",
     "apply_position_change": "ApplyPositionChange (F:331-350)",
-    "hitbox_hurtbox_collision": "UpdateHitboxHurtboxCollision (BC:521-591)",
     "collision_lookup": "UpdateHitboxHurtboxCollision (BC:521-591)",
     "collision_resolve": "UpdateHitboxHurtboxCollision: resolution, NotifyAttackHit, SetHitStun (BC:535-591)",
     "wave_has_hit": "hit gate: wave-wide ballot and branch (scheduling, no C# counterpart)",
@@ -70,6 +69,7 @@ PHASES = {
     "write_final": "outputs: terminal record (FE same-step reset) [rare]",
     "st_off": "outputs: EnvironmentState / obs / info (BC:449-468, FE:336-380)",
     "reset_burst": "KO -> End -> Intro -> Fight burst (BC:212-345) [rare]",
+    "intro_tick": "KO -> End -> Intro -> Fight burst (BC:212-345) [rare]",
     "end_tick": "KO -> End -> Intro -> Fight burst (BC:212-345) [rare]",
     "setup_battle_start": "KO -> End -> Intro -> Fight burst (BC:212-345) [rare]",
     "opaque_burst_results": "KO -> End -> Intro -> Fight burst (BC:212-345) [rare]",
@@ -79,7 +79,6 @@ PHASES = {
     "request_sel_cls": "UpdateActionRequest: request-table index (F:201-286)",
     "next_tick_entry": "next tick's entry read: frame, record, request class (F:140-166, AD:87-168)",
     "tick_entry": "next tick's entry read: frame, record, request class (F:140-166, AD:87-168)",
-    "tick_entry_after_burst": "KO -> End -> Intro -> Fight burst (BC:212-345) [rare]",
     "tick_entry_slow": "next tick's entry from ActionInfo, frames past the table [rare]",
     "settle_w": "action rows: wait for the next tick's row (TrainingRemoteActor input)",
     "row_load": "action rows: load (TrainingRemoteActor input)",
@@ -109,7 +108,7 @@ ENV_STEP_MARKS = [
 RARE_TAG = "[rare]"
 HIT_TAG = " [hit]"  # appended in the specialised loops: runs only on wave-ticks with a hit
 # functions charged wherever they sit in the chain (the rare work nested inside a common phase)
-NESTED = {"notify_damaged", "attack_info", "tick_entry_slow", "tick_entry_after_burst"}
+NESTED = {"notify_damaged", "attack_info", "tick_entry_slow"}
 # small helpers that belong to their caller's phase: charged to the call site's line in env_step
 HELPERS = {"xpair", "xp1", "xp2", "fadd", "fsub", "fadd2", "fsub2", "tabs", "bit0_mask", "splat", "sel4",
            "ai_frame_count", "ai_loop_from", "ai_cancel_lo", "ai_cancel_hi"}

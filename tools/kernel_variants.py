@@ -23,7 +23,7 @@ def _edit_fn(src, signature_start, body_prefix):
     """Insert body_prefix right after the opening brace of the function whose definition
     line contains signature_start."""
     i = src.index(signature_start)
-    j = src.index("{", i)
+    j = src.index(") {\n", i) + 2  # (the body's brace: a default argument such as Pre{} has one too)
     return src[:j + 1] + "\n" + body_prefix + src[j + 1:]
 
 
@@ -60,7 +60,7 @@ VARIANTS = {
     "_const_actions": lambda s: s.replace(
         "    else return src[(uint32_t)t * (uint32_t)p.n_envs + (uint32_t)a];",
         "    else return (uint32_t)(t * 5 + a) & 7u;"),
-    "_no_collision": lambda s: _edit_fn(s, "__device__ __forceinline__ void hitbox_hurtbox_collision(", "  return;"),
+    "_no_collision": lambda s: _edit_fn(s, "__device__ __forceinline__ void collision_resolve(", "  return;"),
     "_no_push": lambda s: _edit_fn(s, "__device__ __forceinline__ void push_character_vs_character(", "  return;"),
     "_no_request": lambda s: _edit_fn(s, "__device__ __forceinline__ void update_action_request(", "  return;"),
 }

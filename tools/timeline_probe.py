@@ -46,7 +46,7 @@ def variant_source():
     a = "  const int l = blockIdx.x * blockDim.x + threadIdx.x;\n  const bool active = l < 2 * p.n_envs;\n"
     assert a in s
     s = s.replace(a, a + "  const uint64_t ts0 = __builtin_amdgcn_s_memrealtime();\n", 1)
-    b = "  if constexpr (FUSED) stage_tables<P2 == FS_P2_BOT || P2 == kActors>();\n"
+    b = "  stage_tables<P2 == FS_P2_BOT || P2 == kActors>();\n"
     assert b in s
     s = s.replace(b, b + "  const uint64_t ts1 = __builtin_amdgcn_s_memrealtime();\n", 1)
     c = ("  if (active) {\n    store_lane<P2>(L, p.st, a);\n"
