@@ -6,7 +6,7 @@ the test-side oracle binding (``oracle/binding.py``) agree on layouts.
 """
 import ctypes as C
 
-FS_ABI_VERSION = 7
+FS_ABI_VERSION = 8
 
 FS_OK = 0
 FS_E_INVALID = -1
@@ -30,6 +30,8 @@ FS_AUTORESET_NEXT_STEP = 1
 
 FS_ACT_HOST = 0
 FS_ACT_DEVICE = 1
+FS_SKIP_RESUME = 2
+FS_SKIP_DEFAULT_MAX_TICKS = 64
 
 FS_STREAM_OWN = C.c_void_p(-1 & 0xFFFFFFFFFFFFFFFF)
 
@@ -106,6 +108,10 @@ class fs_packed_traj(C.Structure):
     _fields_ = [("lanes", C.c_void_p), ("reward", C.c_void_p), ("final_lanes", C.c_void_p)]
 
 
+class fs_skip_out(C.Structure):
+    _fields_ = [("ticks", C.c_void_p), ("pending", C.c_void_p), ("n_pending", C.c_void_p)]
+
+
 class fs_policy(C.Structure):
     _fields_ = [
         ("w1", C.c_void_p), ("b1", C.c_void_p), ("w2", C.c_void_p), ("b2", C.c_void_p), ("w3", C.c_void_p),
@@ -166,6 +172,7 @@ LIB_FUNCTIONS = {
     "fs_set_p2_mode": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     "fs_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
     "fs_step_masked": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
+    "fs_step_skip": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(fs_skip_out)]),
     "fs_step_n": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(fs_outputs)]),
     "fs_step_n_packed": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(fs_packed_traj)]),
     "fs_step_n_policy": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(fs_policy), C.c_void_p, C.POINTER(fs_outputs)]),

@@ -65,6 +65,8 @@ struct fs_context {
   hipEvent_t staging_free = nullptr;
   uint4* delay_ring = nullptr;   // frame_delay > 0: [d][N] x 32-B observation records (fs_delay.hip)
   uint8_t* delay_head = nullptr; // frame_delay > 0: [N] each arena's ring head
+  double* skip_acc = nullptr;    // fs_step_skip: [N] each arena's reward sum of its current decision
+  int32_t* skip_ticks = nullptr; // fs_step_skip: [N] each arena's tick count of its current decision
   std::vector<uint8_t> p2bot;    // host mirror of each arena's P2 actor (1 = the bot)
   bool geom = false;             // the last fs_set_state loaded a fighter with position.y != 0 or a flipped
                                  // facing: steps run the kernels' general-geometry tick
@@ -301,6 +303,10 @@ FS_API int fs_create(const fs_config* cfg, fs_handle* out) {
   // staging
   if ((rc = dalloc(h, &h->d_act, 2 * N)) || (rc = dalloc(h, &h->d_seeds, N)) || (rc = dalloc(h, &h->d_mask, N)))
     return fail(rc);
+  if ((rc = dalloc(h, &h->skip_acc, N)) || (rc = dalloc(h, &h->skip_ticks, N))) return fail(rc);
+  if (hipMemsetAsync(h->skip_acc, 0, N * sizeof(double), h->stream) != hipSuccess ||
+      hipMemsetAsync(h->skip_ticks, 0, N * sizeof(int32_t), h->stream) != hipSuccess)
+    return fail(set_err(h, FS_E_DEVICE, "memset"));
   if (cfg->frame_delay > 0 && ((rc = dalloc(h, &h->delay_ring, 2 * (size_t)cfg->frame_delay * N)) ||
                                (rc = dalloc(h, &h->delay_head, N))))
     return fail(rc);
@@ -577,6 +583,71 @@ FS_API int fs_step_masked(fs_handle h, const uint8_t* p1_act, const uint8_t* p2_
     return set_err(h, FS_E_INVALID, "fs_step_masked: p2 actions required for FS_P2_EXTERNAL");
   if (flags != FS_ACT_HOST && flags != FS_ACT_DEVICE) return set_err(h, FS_E_INVALID, "bad flags %d", flags);
   return step_common(h, 1, p1_act, p2_act, flags, 0, nullptr, active);
+}
+
+FS_API int fs_step_skip(fs_handle h, const uint8_t* p1_act, const uint8_t* active, int flags, int max_ticks,
+                        const fs_skip_out* out) {
+  if (!h) return FS_E_INVALID;
+  if (h->cfg.p2_mode == FS_P2_EXTERNAL)  // (also with every arena switched to the bot: the handle's kind decides)
+    return set_err(h, FS_E_UNSUPPORTED, "fs_step_skip: a remote P2 (FS_P2_EXTERNAL) must answer every frame; the "
+                                        "fused skip runs the in-game bot or an idle P2");
+  if (h->cfg.p1_mode == FS_P1_BOT)
+    return set_err(h, FS_E_UNSUPPORTED, "fs_step_skip: P1 is the bot (FS_P1_BOT): there is no agent decision to "
+                                        "skip to");
+  if (h->cfg.frame_delay > 0)
+    return set_err(h, FS_E_UNSUPPORTED, "fs_step_skip: frame_delay > 0 is not supported (the delayed queue "
+                                        "consumes every tick's row)");
+  if (flags & ~(FS_ACT_DEVICE | FS_SKIP_RESUME)) return set_err(h, FS_E_INVALID, "fs_step_skip: bad flags %d", flags);
+  if (max_ticks < 1) return set_err(h, FS_E_INVALID, "fs_step_skip: max_ticks must be >= 1 (got %d)", max_ticks);
+  const bool resume = (flags & FS_SKIP_RESUME) != 0, device = (flags & FS_ACT_DEVICE) != 0;
+  if (!resume && !p1_act) return set_err(h, FS_E_INVALID, "fs_step_skip: p1 actions required to start a decision");
+  int rc;
+  if ((rc = use_device(h))) return rc;
+  const size_t N = (size_t)h->n;
+  fsk::SkipParams q{};
+  fsk::StepParams& sp = q.p;
+  sp.st = h->st;
+  sp.out = h->out;
+  sp.n_envs = h->n;
+  sp.n_steps = 1;
+  sp.out_stride_steps = 0;
+  sp.dense_reward = h->cfg.dense_reward;
+  sp.autoreset_mode = h->cfg.autoreset_mode;
+  sp.t0 = h->steps;
+  sp.arena_base = h->cfg.arena_base;
+  sp.p2_resets = h->cfg.p2_mode == FS_P2_BOT;
+  sp.p2_noop = h->cfg.p2_mode == FS_P2_NOOP;
+  sp.geom = h->geom;
+  if (device) {
+    sp.p1 = resume ? nullptr : p1_act;
+    sp.active = active;
+  } else if ((!resume && p1_act) || active) {  // host arrays through the staging buffers
+    if ((rc = staging_wait(h))) return rc;
+    if (!resume) {
+      memcpy(h->h_act, p1_act, N);
+      HIP_TRY(h, hipMemcpyAsync(h->d_act, h->h_act, N, hipMemcpyHostToDevice, h->stream));
+      sp.p1 = h->d_act;
+    }
+    if (active) {
+      memcpy(h->h_mask, active, N);
+      HIP_TRY(h, hipMemcpyAsync(h->d_mask, h->h_mask, N, hipMemcpyHostToDevice, h->stream));
+      sp.active = h->d_mask;
+    }
+    HIP_TRY(h, hipEventRecord(h->staging_free, h->stream));
+  }
+  q.acc = h->skip_acc;
+  q.nticks = h->skip_ticks;
+  q.max_ticks = max_ticks;
+  q.resume = resume ? 1 : 0;
+  if (out) {
+    q.ticks_out = out->ticks;
+    q.pending_out = out->pending;
+    q.n_pending = out->n_pending;
+    if (out->n_pending) HIP_TRY(h, hipMemsetAsync(out->n_pending, 0, sizeof(int32_t), h->stream));
+  }
+  HIP_TRY(h, fsk::launch_step_skip(q, h->cfg.float_mode, h->cfg.p2_mode, h->stream));
+  h->steps += 1;
+  return FS_OK;
 }
 
 FS_API int fs_step_n(fs_handle h, int n, const uint8_t* p1_act, const uint8_t* p2_act, uint64_t action_seed,

@@ -101,6 +101,18 @@ struct StepParams {
 };
 constexpr int kInlineArenas = 32;  // sizeof(StepParams::inl[0])
 
+// fs_step_skip (k_step_skip): one launch runs each active arena to its next agent decision
+struct SkipParams {
+  StepParams p;          // p.p1: [N] or null (resume); p.active: [N] or null
+  double* acc;           // [N] the handle's reward sums of the current decision
+  int32_t* nticks;       // [N] the handle's tick counts of the current decision
+  int32_t* ticks_out;    // [N] or null
+  uint8_t* pending_out;  // [N] or null; may alias p.active (read before the loop, written after it)
+  int32_t* n_pending;    // [1] or null: zeroed by the host on the stream ahead of the launch
+  int max_ticks;         // >= 1
+  int resume;            // continue the decision with input 0 from acc / nticks
+};
+
 struct ResetParams {
   DevState st;
   DevOutputs out;
@@ -136,6 +148,8 @@ struct DelayParams {
 hipError_t launch_step(const StepParams& p, int float_mode, int variant, hipStream_t s);
 const char* step_kernel_name(bool policy, bool hashed, int n_steps, int n_envs, int float_mode, int variant,
                              bool geom, bool packed, int autoreset_mode);
+// p2_mode: FS_P2_BOT or FS_P2_NOOP (the handle's fixed P2; fs_step_skip refuses the others)
+hipError_t launch_step_skip(const SkipParams& q, int float_mode, int p2_mode, hipStream_t s);
 hipError_t launch_reset(const ResetParams& p, int float_mode, hipStream_t s);
 hipError_t launch_set_p2(const DevState& st, int bot, const uint8_t* mask, int n, hipStream_t s);
 hipError_t launch_hash_actions(int n_envs, int n_steps, uint64_t seed, uint64_t t0, uint64_t arena_base, uint8_t* p1,

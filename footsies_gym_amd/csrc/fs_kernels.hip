@@ -2189,6 +2189,106 @@ __global__ __launch_bounds__(256) void k_step_n_policy(StepParams p) {
   else step_body<TickCfg<FM, P2, kPolicy>>(p);
 }
 
+// fs_step_skip: one agent decision per arena under the reference's frame-skip wrapper
+// (wrappers/frame_skip.py:46-80).  After the tick that takes the agent's action, each arena keeps
+// ticking with no input while its own observation says P1 cannot act (is_skippable below) and the
+// episode goes on, so the two lanes of an arena leave the loop after that arena's own number of
+// ticks -- a divergent loop, which the row loops cannot express.  The tick is the generic one on
+// the LDS tables, unchanged (the hashed kernels' parameter list): it carries the tick entry, not
+// the ActionInfo that step_one fetches from other lanes of a full wave.
+//
+// The sum of the ticks' rewards is the wrapper's left-to-right f64 sum from 0.0.  The tick stores
+// its reward itself and does not return it, so the loop hands it a reward row that maps this
+// lane's arena onto a slot of LDS, reads the slot back after the tick, and stores the sum once
+// behind the loop; the tick's other outputs go to the arena's output row every tick, the last
+// one's staying (same lane, same address, program order).
+//
+// The loop ends on a terminal tick by itself in same-step auto-reset (the observation is then
+// state(-1): STAND, never skippable); in next-step mode the terminal tick leaves `pending` set,
+// which is the test here, and a pending arena's next tick is the reset burst alone.
+// (SkipParams: fs_internal.h.)
+
+// wrappers.is_skippable (frame_skip.py:49-61) on the observation write_obs stores, the same on both
+// lanes of the pair: P1's observed move_frame != 0 and P2's observed move none of DAMAGE / GUARD_*,
+// or P1's observed move DAMAGE.
+__device__ __forceinline__ bool is_skippable(const Lane& L) {
+  int m = L.f.act;
+  if (m == A_DEAD || m == A_WIN) m = A_STAND;  // FE:537-549
+  const int mf = (m == A_STAND || m == A_FORWARD || m == A_BACKWARD) ? 0 : L.f.frame;  // FE:339-358
+  const uint32_t mine = (uint32_t)m | ((uint32_t)(mf != 0) << 8);
+  const uint32_t p1 = xp1(mine), p2 = xp2(mine);
+  constexpr uint32_t kHitGuard = (1u << A_DAMAGE) | (1u << A_GUARD_STAND) | (1u << A_GUARD_CROUCH) |
+                                 (1u << A_GUARD_M) | (1u << A_GUARD_BREAK);
+  const bool p2_hit_or_guarding = ((kHitGuard >> (p2 & 0xffu)) & 1u) != 0;
+  return ((p1 >> 8) != 0 && !p2_hit_or_guarding) || (p1 & 0xffu) == (uint32_t)A_DAMAGE;
+}
+
+__shared__ double sSkipReward[kBlock];  // each lane's reward of the tick it just ran
+template <class C>
+__device__ __forceinline__ void skip_body(const SkipParams& q) {
+  constexpr int P2 = C::P2;
+  static_assert(C::TP == kTabLds && (P2 == FS_P2_BOT || P2 == FS_P2_NOOP), "fs_step_skip: the bot or an idle P2");
+  const StepParams& p = q.p;
+  const int l = blockIdx.x * kBlock + threadIdx.x;
+  const bool in_range = l < 2 * p.n_envs;
+  const int a = in_range ? l >> 1 : 0;
+  const uint32_t k = l & 1;
+  Lane L;
+  load_lane<P2>(L, p.st, a, k);
+  if constexpr (C::GEOM) L.f.y = reinterpret_cast<const float*>(p.st.posy)[2 * a + (int)k];
+  const uint32_t on = p.active ? p.active[a] : 1u;
+  uint32_t in = 0;
+  double acc = 0.0;
+  int n = 0;
+  if (q.resume) {
+    acc = q.acc[a];
+    n = q.nticks[a];
+  } else {
+    in = p.p1[a] & 7u;
+  }
+  stage_tables<P2 == FS_P2_BOT>();
+  if (!in_range || !on) return;
+  L.te = next_tick_entry<false>(L.f);
+  // the tick's reward row: arena a's element is this lane's slot of sSkipReward (a flat address
+  // computed in integers and made opaque, so the tick's store and the read below are the same kind
+  // of access to the same address; the tick adds 8 a back)
+  uintptr_t row = reinterpret_cast<uintptr_t>(&sSkipReward[threadIdx.x]) - 8ull * (uint32_t)a;
+  asm volatile("" : "+v"(row));
+  StepParams ps = p;
+  ps.out.reward = reinterpret_cast<double*>(row);
+  uint32_t none = 0;
+  int ran = 0;
+  bool more;
+  do {
+    env_step<FS_TICK(C)>(L, in, ps, (uint32_t)a, none);
+    acc += ps.out.reward[a];
+    n++;
+    ran++;
+    in = 0;
+    more = is_skippable(L) && !L.pending;
+  } while (more && ran < q.max_ticks);
+  store_lane<P2>(L, p.st, a);
+  if constexpr (C::GEOM) reinterpret_cast<float*>(p.st.posy)[2 * a + (int)k] = L.f.y;
+  // one add per wave for its arenas still pending (the lanes of the wave meet again here)
+  const uint64_t still = __builtin_amdgcn_ballot_w64(more && k == 0);
+  if (k == 0) {
+    p.out.reward[a] = acc;
+    q.acc[a] = acc;
+    q.nticks[a] = n;
+    if (q.ticks_out) q.ticks_out[a] = n;
+    if (q.pending_out) q.pending_out[a] = more ? 1 : 0;
+    if (q.n_pending && more && (still & ((1ull << (threadIdx.x & 63u)) - 1ull)) == 0)
+      atomicAdd(q.n_pending, (int32_t)__builtin_popcountll(still));
+  }
+}
+
+// (the general-geometry tick behind a launch-uniform branch, as in k_step_n)
+template <int FM, int P2>
+__global__ __launch_bounds__(256) void k_step_skip(SkipParams q) {
+  if (q.p.geom) skip_body<TickCfg<FM, P2, kHashed, kGeom>>(q);
+  else skip_body<TickCfg<FM, P2, kHashed>>(q);
+}
+
 // FootsiesEnv.reset (FE:482-515) / RESET (BC:143-146) / game start (BC:105-128), every handle
 // kind through the per-arena actor logic (off the throughput path).
 template <int FM>
@@ -2598,6 +2698,21 @@ hipError_t launch_get_state(const DevState& st, fs_arena_state* dst, fs_env_stat
 
 hipError_t launch_set_state(const DevState& st, const fs_arena_state* src, int n, hipStream_t s) {
   hipLaunchKernelGGL(k_set_state, grid_for(n), dim3(kBlock), 0, s, st, src, n);
+  return hipGetLastError();
+}
+
+// (named last: the device code numbers the kernels in the order the host first names them, and the
+// step kernels keep their numbers -- DESIGN.md "The identity rule")
+template <int FM>
+static void launch_step_skip_fm(const SkipParams& q, int p2_mode, hipStream_t s) {
+  const dim3 grid = grid_for(2 * q.p.n_envs), block(kBlock);
+  if (p2_mode == FS_P2_BOT) hipLaunchKernelGGL((k_step_skip<FM, FS_P2_BOT>), grid, block, 0, s, q);
+  else hipLaunchKernelGGL((k_step_skip<FM, FS_P2_NOOP>), grid, block, 0, s, q);
+}
+
+hipError_t launch_step_skip(const SkipParams& q, int float_mode, int p2_mode, hipStream_t s) {
+  if (float_mode == FS_FLOAT_DOUBLE) launch_step_skip_fm<FS_FLOAT_DOUBLE>(q, p2_mode, s);
+  else launch_step_skip_fm<FS_FLOAT_STRICT32>(q, p2_mode, s);
   return hipGetLastError();
 }
 

@@ -270,6 +270,81 @@ class FootsiesSim:
             check(lib().fs_step_masked(self._h, a1.ctypes.data, q2, m.ctypes.data, _abi.FS_ACT_HOST), self._h)
         return self._ready_out()
 
+    def _skip_buffers(self):
+        """skip_ticks (int32 [N]), skip_pending (uint8 [N]) and skip_n_pending (int32 [1]) of
+        step_skip, allocated once: device tensors, or -- without torch -- numpy views of pinned,
+        device-mapped host memory (fs_host_alloc)."""
+        if getattr(self, "_skip_out", None) is not None:
+            return self._skip_out
+        n = self.num_envs
+        if self._native:
+            total = 4 * n + 4 + n  # ticks | n_pending | pending
+            hp, dp = C.c_void_p(), C.c_void_p()
+            check(lib().fs_host_alloc(self._dev_index, total, C.byref(hp), C.byref(dp)), None)
+            raw = (C.c_uint8 * total).from_address(hp.value)
+            raw._owner = _HostBuffer(hp.value)
+            host = np.frombuffer(raw, dtype=np.uint8)
+            self.skip_ticks = host[:4 * n].view(np.int32)
+            self.skip_n_pending = host[4 * n:4 * n + 4].view(np.int32)
+            self.skip_pending = host[4 * n + 4:]
+            # (the count is summed on the host from skip_pending: no device atomics on host memory)
+            self._skip_out = _abi.fs_skip_out(ticks=dp.value, pending=dp.value + 4 * n + 4, n_pending=None)
+        else:
+            torch = _torch()
+            with torch.cuda.device(self.device):
+                self.skip_ticks = torch.zeros(n, dtype=torch.int32, device=self.device)
+                self.skip_pending = torch.zeros(n, dtype=torch.uint8, device=self.device)
+                self.skip_n_pending = torch.zeros(1, dtype=torch.int32, device=self.device)
+            self._skip_out = _abi.fs_skip_out(ticks=self.skip_ticks.data_ptr(), pending=self.skip_pending.data_ptr(),
+                                              n_pending=self.skip_n_pending.data_ptr())
+        return self._skip_out
+
+    def step_skip(self, p1, active=None, max_ticks=_abi.FS_SKIP_DEFAULT_MAX_TICKS, resume=False):
+        """One agent decision of every (or every ``active``) arena in one launch (fs_step_skip):
+        the tick that takes ``p1``, then no-input ticks while the arena's observation is skippable
+        (wrappers.is_skippable) and its episode goes on, at most ``max_ticks`` in this call.  The
+        outputs hold each arena's last tick with ``reward`` the float64 sum over its ticks.
+        ``skip_ticks`` / ``skip_pending`` / ``skip_n_pending`` then hold each arena's tick count,
+        whether it is still skippable at the cap, and how many are (skip_pending_count reads it).
+        ``resume=True`` continues those arenas with no input (``p1`` is ignored):
+        ``step_skip(None, active=sim.skip_pending, resume=True)`` until the count is 0.
+        Actions and mask: device tensors or host arrays, like ``step``."""
+        out = self._skip_buffers()
+        n = self.num_envs
+        flag = _abi.FS_SKIP_RESUME if resume else 0
+        if p1 is None and not resume:
+            raise ValueError("p1 actions are required unless resume=True")
+        torch = None if self._native else _torch()
+        on_device = torch is not None and any(isinstance(x, torch.Tensor) and x.is_cuda for x in (p1, active))
+        if on_device:
+            q1 = None if resume else _as_u8_device(_to_device(p1, self.device), n)
+            m = None if active is None else torch.as_tensor(active, device=self.device).reshape(n).to(
+                torch.uint8).contiguous()
+            check(lib().fs_step_skip(self._h, None if q1 is None else C.c_void_p(q1.data_ptr()),
+                                     None if m is None else C.c_void_p(m.data_ptr()), _abi.FS_ACT_DEVICE | flag,
+                                     int(max_ticks), C.byref(out)), self._h)
+            return self._ready_out()
+        a1 = None if resume else np.ascontiguousarray(encode_actions(_host(p1)))
+        if a1 is not None and a1.shape[0] != n:
+            raise ValueError("expected %d actions" % n)
+        m = None if active is None else np.ascontiguousarray(np.asarray(_host(active)).reshape(n), dtype=np.uint8)
+        check(lib().fs_step_skip(self._h, None if a1 is None else a1.ctypes.data, None if m is None else m.ctypes.data,
+                                 _abi.FS_ACT_HOST | flag, int(max_ticks), C.byref(out)), self._h)
+        if self._native:  # (the pinned arrays are the kernel's destination: wait, then count on the host)
+            check(lib().fs_sync(self._h), self._h)
+            live = self.skip_pending if m is None else self.skip_pending[m != 0]
+            self.skip_n_pending[0] = int(np.count_nonzero(live))
+        return self._ready_out()
+
+    def skip_pending_count(self):
+        """Arenas the last step_skip left pending (skip_n_pending on the host: a 4-byte copy that
+        waits for the handle's stream)."""
+        if self._native:
+            return int(self.skip_n_pending[0])
+        torch = _torch()
+        with torch.cuda.stream(self._stream):
+            return int(self.skip_n_pending.item())
+
     def _check_device(self, t, name, dtype, numel):
         """A buffer the kernels read or write through its raw pointer: a contiguous torch tensor of
         `dtype` on this handle's GPU with at least `numel` elements (anything else would hand the

@@ -327,6 +327,7 @@ class FootsiesVectorEnv(_VectorEnvBase):
         self.reward_range = (-1, 1)
         self.closed = False
         self._last = None  # most recent (obs, info) for the opponent callable
+        self.last_skip_ticks = None  # step_skipped: ticks each arena ran for its last decision
 
     # -- gymnasium.vector.VectorEnv API ---------------------------------------------------
     def reset(self, *, seed=None, options=None):
@@ -420,6 +421,43 @@ class FootsiesVectorEnv(_VectorEnvBase):
         host["terminated"][idle] = 0
         host["truncated"][idle] = 0
         obs, rew, term, trunc, info = step_result_from_outputs(host, self.autoreset_mode)
+        self._last = (obs, info)
+        return obs, rew, term, trunc, info
+
+    def skip_refusal(self):
+        """Why step_skipped cannot run on this environment (a message), or None."""
+        if self.sim.p2_mode == "external":
+            return "a callable opponent must answer every frame"
+        if self.by_example:
+            return "by_example: the bot plays P1, there is no agent decision to skip to"
+        if int(self.sim.cfg.frame_delay) > 0:
+            return "frame_delay > 0: the delayed queue consumes every tick's row"
+        return None
+
+    def step_skipped(self, actions, max_ticks=_abi.FS_SKIP_DEFAULT_MAX_TICKS):
+        """step() under the reference's frame-skip wrapper (frame_skip.py:63-80), fused
+        (fs_step_skip): after the agent's action each arena keeps ticking with no input while its
+        observation is skippable (wrappers.is_skippable) and its episode goes on, all inside one
+        kernel launch -- more launches only while some arena is still skippable after ``max_ticks``
+        ticks.  Returns step()'s 5-tuple of each arena's last tick with the rewards summed (float64,
+        in tick order); ``last_skip_ticks`` holds each arena's tick count."""
+        self._check_open()
+        why = self.skip_refusal()
+        if why is not None:
+            raise ValueError("step_skipped: " + why)
+        sim = self.sim
+        out = sim.step_skip(actions, max_ticks=max_ticks)
+        while sim.skip_pending_count():
+            out = sim.step_skip(None, active=sim.skip_pending, max_ticks=max_ticks, resume=True)
+        if self.output == "torch":
+            self.last_skip_ticks = sim.skip_ticks
+            obs = {k: out[k] for k in ("guard", "move", "move_frame", "position")}
+            self._last = (obs, out)
+            return obs, out["reward"], out["terminated"], out["truncated"], out
+        self.last_skip_ticks = (sim.skip_ticks.copy() if isinstance(sim.skip_ticks, np.ndarray)
+                                else sim.skip_ticks.cpu().numpy())
+        obs, rew, term, trunc, info = step_result_from_outputs(sim.outputs_numpy(copy=False, _synced=True),
+                                                               self.autoreset_mode)  # (the count's read waited)
         self._last = (obs, info)
         return obs, rew, term, trunc, info
 

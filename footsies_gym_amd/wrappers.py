@@ -8,6 +8,8 @@ applies, per arena, what the reference wrapper does to one FootsiesEnv:
                                                                     move_frame / move duration
   FootsiesFrameSkipped                   frame_skip.py:6-80         no-op through frames where P1
                                                                     cannot act, summing rewards
+                                                                    (fused=True: inside one kernel
+                                                                    launch, step_skipped)
   FootsiesStatistics                     statistics.py:5-70         special-move counts per episode
 
 Auto-reset: the vector env resets finished arenas itself ("same_step" or
@@ -58,6 +60,10 @@ class VectorWrapper:
     def step_masked(self, actions, active):
         return self.env.step_masked(actions, active)
 
+    def step_skipped(self, actions):
+        """FootsiesVectorEnv.step_skipped (the fused frame skip) through this wrapper."""
+        return self.env.step_skipped(actions)
+
     def close(self):
         return self.env.close()
 
@@ -95,6 +101,9 @@ class FootsiesActionCombinationsDiscretized(VectorWrapper):
 
     def step_masked(self, actions, active):
         return self.env.step_masked(self.action(actions), active)
+
+    def step_skipped(self, actions):
+        return self.env.step_skipped(self.action(actions))
 
 
 def _decimal_f64(x):
@@ -151,6 +160,9 @@ class FootsiesNormalized(VectorWrapper):
     def step_masked(self, actions, active):
         return self._wrap(self.env.step_masked(actions, active))
 
+    def step_skipped(self, actions):
+        return self._wrap(self.env.step_skipped(actions))
+
     @staticmethod
     def undo(obs, normalized_guard=True):
         """Inverse transform (normalization.py:44-55)."""
@@ -184,18 +196,39 @@ class FootsiesFrameSkipped(VectorWrapper):
     its observation is skippable and the episode goes on; the rewards of those frames
     are summed into the step's reward (frame_skip.py:63-80).  Arenas advance at their
     own pace through fs_step_masked, so each one sees exactly the tick sequence of a
-    separately wrapped FootsiesEnv.  Apply on top of FootsiesNormalized, not below it."""
+    separately wrapped FootsiesEnv.  Apply on top of FootsiesNormalized, not below it.
 
-    def __init__(self, env):
+    ``fused=True``: the whole skip runs inside the simulator (FootsiesVectorEnv.step_skipped, one
+    kernel launch per agent decision) instead of one masked step per skipped frame, with the same
+    results bit for bit.  It needs a chain down to a FootsiesVectorEnv that offers step_skipped
+    (the in-game bot or "noop" as P2, no frame_delay, no by_example) without a per-tick wrapper
+    (FootsiesStatistics) in it: ValueError otherwise."""
+
+    def __init__(self, env, fused=False):
         super().__init__(env)
         self.single_observation_space = sp.frame_skipped_observation_space(env.single_observation_space)
         self._noop = np.zeros(self.num_envs, dtype=np.uint8)
+        self.fused = bool(fused)
+        if self.fused:
+            e = env
+            while isinstance(e, VectorWrapper):
+                if isinstance(e, FootsiesStatistics):
+                    raise ValueError("fused frame skip: FootsiesStatistics counts per tick and cannot sit under it")
+                e = e.env
+            if not callable(getattr(e, "step_skipped", None)):
+                raise ValueError("fused frame skip: %s offers no step_skipped" % type(e).__name__)
+            why = e.skip_refusal() if callable(getattr(e, "skip_refusal", None)) else None
+            if why is not None:
+                raise ValueError("fused frame skip: " + why)
 
     def reset(self, *, seed=None, options=None):
         obs, info = self.env.reset(seed=seed, options=options)
         return frame_skip_obs(obs), info  # no skipping on the first state (frame_skip.py:65-69)
 
     def step(self, actions):
+        if self.fused:
+            obs, rew, term, trunc, info = self.env.step_skipped(actions)
+            return frame_skip_obs(obs), rew, term, trunc, _map_final(info, frame_skip_obs)
         obs, rew, term, trunc, info = self.env.step(actions)
         obs = {k: np.array(v) for k, v in obs.items()}
         total = 0.0 + np.asarray(rew, dtype=np.float64)
@@ -288,6 +321,10 @@ class FootsiesStatistics(VectorWrapper):
         res = self.env.step_masked(actions, active)
         self._count(res[0], res[2], res[3], res[4], rows=active)
         return res
+
+    def step_skipped(self, actions):
+        raise TypeError("FootsiesStatistics counts per tick and cannot sit under a fused frame skip "
+                        "(FootsiesFrameSkipped(..., fused=True) / step_skipped)")
 
     @property
     def metric_special_moves_per_episode(self):

@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define FS_ABI_VERSION 7
+#define FS_ABI_VERSION 8
 
 /* error codes */
 #define FS_OK 0
@@ -262,6 +262,43 @@ int fs_step(fs_handle h, const uint8_t* p1_act, const uint8_t* p2_act, int flags
  * where flags says the actions do.  With frame_delay > 0 each arena's delayed-frame
  * queue advances with that arena's own steps (every FootsiesEnv keeps its own deque). */
 int fs_step_masked(fs_handle h, const uint8_t* p1_act, const uint8_t* p2_act, const uint8_t* active, int flags);
+
+/* One agent decision per arena under the reference's frame-skip wrapper
+ * (wrappers/frame_skip.py:46-80), in one kernel launch: each active arena runs the tick that
+ * takes p1_act[i], then keeps ticking with input 0 while its own observation is skippable --
+ * P1's observed move_frame != 0 and P2's observed move none of DAMAGE / GUARD_STAND /
+ * GUARD_CROUCH / GUARD_M / GUARD_BREAK, or P1's observed move DAMAGE (frame_skip.py:49-61) --
+ * and the episode goes on, at most max_ticks ticks in this call.  Every tick is fs_step's
+ * (auto-reset burst, final_* records, the bot, the cumulative reward); the rewards are summed in
+ * float64 in tick order from 0.0, as frame_skip.py:71-78 sums them.  Afterwards the handle's
+ * regular or bound outputs hold each active arena's last tick with `reward` set to the sum; in
+ * FS_AUTORESET_SAME_STEP final_* holds the terminal record of an arena that ended.  A
+ * FS_AUTORESET_NEXT_STEP arena with a reset pending runs the reset burst alone (state(-1), reward
+ * 0: never skippable).
+ *   active: [N] 0/1 or NULL (all arenas), living where flags says the actions live.  Inactive arenas
+ *     keep their state, outputs, accumulators and their ticks / pending entries (fs_step_masked).
+ *   flags: FS_ACT_HOST or FS_ACT_DEVICE, optionally | FS_SKIP_RESUME.  Without FS_SKIP_RESUME p1_act
+ *     is required and a new decision starts for the active arenas.  With it p1_act is ignored (may
+ *     be NULL) and the active arenas continue their decision with input 0 from the handle's
+ *     accumulators: a caller loops
+ *       fs_step_skip(h, NULL, out.pending, FS_ACT_DEVICE | FS_SKIP_RESUME, cap, &out)
+ *     until n_pending is 0.  Any split into caps gives results bit-identical to one uncapped call,
+ *     the reward sum and final_* included.
+ *   out: optional device arrays, each optional.
+ * fs_steps_taken advances by 1 per call (as fs_step_masked).  Asynchronous on the handle's stream.
+ * FS_E_UNSUPPORTED for a handle created with FS_P2_EXTERNAL (a remote P2 must answer every frame;
+ * also after fs_set_p2_mode), for FS_P1_BOT, and with frame_delay > 0 (the delayed queue consumes
+ * every tick's row).  FS_E_INVALID for max_ticks < 1, a missing p1_act without FS_SKIP_RESUME, or
+ * unknown flag bits.  (ABI 8) */
+#define FS_SKIP_RESUME 2   /* or'd into flags beside FS_ACT_HOST / FS_ACT_DEVICE */
+#define FS_SKIP_DEFAULT_MAX_TICKS 64
+typedef struct fs_skip_out {
+  int32_t* ticks;      /* [N] device, optional: ticks this arena ran for the current decision (all resumes included) */
+  uint8_t* pending;    /* [N] device, optional: 1 = still skippable at the cap; may alias `active` */
+  int32_t* n_pending;  /* [1] device, optional: set (not added) to the number of pending arenas of this call */
+} fs_skip_out;
+int fs_step_skip(fs_handle h, const uint8_t* p1_act, const uint8_t* active, int flags, int max_ticks,
+                 const fs_skip_out* out);
 
 /* n Fight ticks in one kernel launch (fused rollout).  Actions: device arrays
  * [n][N], or NULL to draw them on device from the counter-based hash
