@@ -3,7 +3,7 @@ ranks sharing cuda:0 over a gloo group, each a PPOTrainer(group=...) over its ow
 (arena_base = rank x 4 096).  The ranks start from rank 0's weights and stay bit-identical through
 training; the advantages are normalised over both ranks together; and one minibatch's averaged
 gradient equals fs_ppo_grad over both ranks' minibatch rows in one call, up to fp32 summation
-order.  (The driver's multi-GPU bench runs the same trainer over RCCL: bench.py's ppo_dp leg.)"""
+order -- in both learner precisions, fp32 and the trainer's default split_bf16.  (The driver's multi-GPU bench runs the same trainer over RCCL: bench.py's ppo_dp leg.)"""
 import os
 import socket
 
@@ -28,7 +28,7 @@ def flat_weights(tr):
     return torch.cat([p.detach().reshape(-1) for p in list(tr.actor.parameters()) + list(tr.critic.parameters())])
 
 
-def worker(rank, port, q):
+def worker(rank, port, q, precision):
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
     import torch
     import torch.distributed as dist
@@ -38,14 +38,14 @@ def worker(rank, port, q):
     from footsies_gym_amd.simulator import FootsiesSim
     sim = FootsiesSim(N, device=0, p2_mode="bot", seed=0, arena_base=rank * N)
     # seed = rank: each rank would draw its own initial weights; the trainer starts from rank 0's
-    tr = PPOTrainer(sim, horizon=T, group="default", learner_precision="fp32", seed=rank)
+    tr = PPOTrainer(sim, horizon=T, group="default", learner_precision=precision, seed=rank)
     w0 = flat_weights(tr).cpu().numpy()
     tr.train(2)
     w2 = flat_weights(tr).cpu().numpy()
     loss = tr.stats["loss"].item()
     rows, _ = tr.prepare(*tr.collect())
     mb = rows[:K].contiguous()
-    pg = PPOGrad(tr.actor, tr.critic, precision="fp32")
+    pg = PPOGrad(tr.actor, tr.critic, precision=precision)
     pg(mb, tr.clip, tr.vf_coef, tr.ent_coef)
     g_local = pg.grad.clone()
     g_dp = allreduce_mean_(pg.grad.clone()).cpu().numpy()
@@ -63,12 +63,20 @@ def worker(rank, port, q):
     dist.destroy_process_group()
 
 
-def test_data_parallel_ppo_two_ranks_on_one_gpu():
+# g_dp against g_cat, as a fraction of the joint gradient's largest entry: the two differ by fp32
+# summation order (fp32), and under split_bf16 -- the trainer's default, what bench.py's ppo_dp runs
+# -- also by the bf16 split's dropped lo x lo terms, 10 x the fp32 bar as in tests/test_gpu_learn.py
+# (ATOL_FRAC).  Measured on an MI355X: 6.3e-8 (fp32) and 1.3e-7 (split_bf16); printed by the test.
+DP_TOL = {"fp32": 2e-5, "split_bf16": 2e-4}
+
+
+@pytest.mark.parametrize("precision", ["fp32", "split_bf16"])
+def test_data_parallel_ppo_two_ranks_on_one_gpu(precision):
     import torch.multiprocessing as mp
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
     port = free_port()
-    procs = [ctx.Process(target=worker, args=(r, port, q)) for r in range(WORLD)]
+    procs = [ctx.Process(target=worker, args=(r, port, q, precision)) for r in range(WORLD)]
     for p in procs:
         p.start()
     got = {}
@@ -88,7 +96,9 @@ def test_data_parallel_ppo_two_ranks_on_one_gpu():
     assert not np.array_equal(a["g_local"], b["g_local"])
     assert a["g_dp"].tobytes() == b["g_dp"].tobytes()
     scale = np.abs(a["g_cat"]).max()
-    assert np.abs(a["g_dp"] - a["g_cat"]).max() <= 2e-5 * scale, (np.abs(a["g_dp"] - a["g_cat"]).max(), scale)
+    gap = np.abs(a["g_dp"] - a["g_cat"]).max()
+    print("data-parallel %s: max |g_dp - g_cat| = %.3e x the largest gradient entry" % (precision, gap / scale))
+    assert gap <= DP_TOL[precision] * scale, (gap, scale)
     # advantages normalised over both ranks together (each rank alone is not centred)
     adv = a["adv"].astype(np.float64)
     assert abs(adv.mean()) < 1e-5 and abs(adv.std(ddof=1) - 1.0) < 1e-4, (adv.mean(), adv.std(ddof=1))

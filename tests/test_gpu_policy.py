@@ -22,9 +22,11 @@ MARGIN = 5e-3  # probability distance from a CDF boundary below which a neighbou
 LOGP_TOL = 0.05
 
 
-def _check_policy(params, seed, prev, acts, logps, t0, N):
-    """prev: outputs before the first tick; acts/logps: [T][N]; returns the next `prev` source."""
-    agreed = checked = 0
+def _check_policy(params, seed, prev, acts, logps, t0, N, logp_tol=LOGP_TOL):
+    """prev: outputs before the first tick; acts/logps: [T][N].  Returns (mean, max) of |d logp|
+    over the draws that agree with the restatement's."""
+    agreed = checked = n_same = 0
+    total, worst, worst_t = 0.0, 0.0, 0
     for t in range(len(acts)):
         f = policy_ref.features(prev[t])
         lg = policy_ref.logits(params, f)
@@ -35,9 +37,13 @@ def _check_policy(params, seed, prev, acts, logps, t0, N):
         agreed += int((act[ok] == acts[t][ok]).sum())
         same = act == acts[t]
         err = np.abs(logp[same] - logps[t][same])
-        assert err.max() < LOGP_TOL, (t, float(err.max()))
+        n_same, total = n_same + int(same.sum()), total + float(err.sum(dtype=np.float64))
+        if err.size:  # (no agreeing draw in a tick: the action comparison below reports it)
+            worst, worst_t = max((worst, worst_t), (float(err.max()), t))
+    assert worst < logp_tol, (worst_t, worst, total / n_same)  # (tick, its max, the mean over all ticks)
     assert checked > 0.9 * N * len(acts), checked  # 7 boundaries x 2 x MARGIN ~ 7% fall inside
     assert agreed == checked, "%d of %d actions differ away from CDF boundaries" % (checked - agreed, checked)
+    return total / n_same, worst
 
 
 @pytest.mark.parametrize("p2,autoreset", [("bot", "same_step"), ("external", "next_step"), ("noop", "same_step")])
@@ -83,9 +89,10 @@ FP32_KL = 1e-3
 FP32_MARGIN = 0.02
 
 
-def _check_fp32(actor, prev, acts, logps, seed, t0, N):
+def _check_fp32(actor, prev, acts, logps, seed, t0, N, check=True):
     """Kernel samples / log-probs vs the fp32 actor on the same (f32) features; returns the
-    per-tick sample estimate of KL(kernel actor || fp32 actor) and the max |d logp|."""
+    per-tick sample estimate of KL(kernel actor || fp32 actor) and the max |d logp|.
+    (check=False: the numbers only, for a report.)"""
     import torch
     dev = next(actor.parameters()).device
     kls, worst, agreed, checked, mean_abs = [], 0.0, 0, 0, []
@@ -103,12 +110,60 @@ def _check_fp32(actor, prev, acts, logps, seed, t0, N):
         worst = max(worst, float(np.abs(d).max()))
         mean_abs.append(float(np.abs(d).mean()))
         kls.append(float(d.mean()))
-    assert checked > 0.6 * N * len(acts), checked
-    assert agreed == checked, "%d of %d draws differ from the fp32 actor's away from CDF boundaries" % (
-        checked - agreed, checked)
-    assert worst < FP32_LOGP_MAX, worst
-    assert np.mean(mean_abs) < FP32_LOGP_MEAN, np.mean(mean_abs)
+    if check:
+        assert checked > 0.6 * N * len(acts), checked
+        assert agreed == checked, "%d of %d draws differ from the fp32 actor's away from CDF boundaries" % (
+            checked - agreed, checked)
+        assert worst < FP32_LOGP_MAX, worst
+        assert np.mean(mean_abs) < FP32_LOGP_MEAN, np.mean(mean_abs)
     return kls, worst, float(np.mean(mean_abs))
+
+
+SCALED_LOGP_MEAN = 1e-3  # a wrong fold or fragment order moves every sample by O(0.1); rounding flips are rare
+SCALED_LOGP_TOL = {3: LOGP_TOL, 8: LOGP_TOL}  # (the measured maxima stay below it: see the test)
+
+
+@pytest.mark.parametrize("scale", [3, 8])
+def test_fused_policy_scaled_actor(oracle_lib, scale):
+    """The kernel actor where PPO takes the weights (tests/ppo_ref.scaled_nets: every parameter x 3 and
+    x 8; half, then most, hidden units saturated, log-probs down to -100): 1025 arenas (a part-filled
+    last wave) x 48 ticks in one launch against the bot.  The bars are the init-weight test's: the
+    sampled actions replay bit-exactly through the oracle, and the kernel matches its bf16
+    restatement (MARGIN, LOGP_TOL) -- which is where the fold b + sum_k W[., k] with -2 W weights
+    cancels large terms (at scale 8 a row sum of W2 is tens, its bias a few).  Not every action
+    need be drawn from a peaked policy.  Added: the mean |d logp| over agreeing draws stays below
+    1e-3.  Measured on an MI355X: mean 4.1e-6 (scale 3) and 1.6e-5 (scale 8), max 6.8e-3 and 1.6e-2,
+    so LOGP_TOL stands as it is.  The gap to the fp32 torch actor is a property of bf16 at this
+    scale, not a bar: it is printed (mean |d logp| 2.5e-2 and 3.4e-2, max 0.23 and 0.97, KL per tick
+    6.8e-4 and 3.1e-3)."""
+    import torch
+    from footsies_gym_amd.rollout import FusedPolicyRollout
+    from footsies_gym_amd.simulator import FootsiesSim
+    from tests.ppo_ref import scaled_nets
+    N, T, seed = 1025, 48, 0xC0FFEE
+    sim = FootsiesSim(N, p2_mode="bot", autoreset_mode="same_step", seed=21)
+    ora = oracle_lib.Oracle(N, p2_mode=P2_MODES["bot"], autoreset_mode=AUTORESET["same_step"], base_seed=21)
+    actor = scaled_nets(9, scale, device=torch.device("cuda", 0))[0]
+    ro = FusedPolicyRollout(sim, actor, seed=seed)
+    params = [p.cpu().numpy() for p in ro.params]
+    prev0 = sim.outputs_numpy()
+    traj = sim.alloc_trajectory(T)
+    acts, logps = ro.rollout(T, trajectory=traj)
+    torch.cuda.synchronize()
+    tr = {k: v.cpu().numpy() for k, v in traj.items()}
+    A, LP = acts.cpu().numpy(), logps.cpu().numpy()
+    assert np.isfinite(LP).all() and LP.max() <= 0.0
+    for t in range(T):
+        compare_outputs(ora.step(A[t]), {k: v[t] for k, v in tr.items()}, step=t, same_step=True)
+    assert sim.steps_taken == T
+    compare_states(ora.state(), sim.get_state())
+    prev = [prev0] + [{k: v[t] for k, v in tr.items()} for t in range(T - 1)]
+    mean_err, worst = _check_policy(params, seed, prev, A, LP, 0, N, logp_tol=SCALED_LOGP_TOL[scale])
+    kls, worst32, mean32 = _check_fp32(actor, prev, A, LP, seed, 0, N, check=False)
+    print("scale %d, %d x %d: kernel vs restatement |d logp| mean %.2e max %.3e; vs the fp32 actor KL per tick %.2e, "
+          "|d logp| max %.3e mean %.2e; min logp %.1f, %d actions drawn" % (
+              scale, N, T, mean_err, worst, np.mean(kls), worst32, mean32, LP.min(), len(np.unique(A))))
+    assert mean_err < SCALED_LOGP_MEAN, mean_err
 
 
 def test_fused_policy_c5_full_size(oracle_lib):
