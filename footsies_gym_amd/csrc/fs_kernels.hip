@@ -1575,6 +1575,9 @@ __device__ __forceinline__ void prio_slice(uint32_t grp) {
 // (a loaded state: a winner, a fighter on the ground, frame 64+, vital 0 or 2-3) sends its wave to the
 // generic loop.
 constexpr int kLmGeneric = 0;   // every test at run time
+#ifndef FS_ROW_DEPTH2
+#define FS_ROW_DEPTH2 4  // the slots of the specialised loops' row ring (row_ring), 2 .. 4
+#endif
 constexpr int kLmFast = 1;      // the common case, no priority slices (one wave per SIMD)
 constexpr int kLmFastPrio = 2;  // the common case with priority slices
 // Is the fighter inside I?  (Tested once per launch, in step_body's prologue.)
@@ -1644,9 +1647,12 @@ __device__ __forceinline__ void prepare_request(Lane& L, uint32_t in, Pre& pre) 
 enum StepKind { kOneTick, kRows, kHashed, kPolicy };
 constexpr unsigned kGeom = 1, kPacked = 2, kPrefetch = 4;
 constexpr int kWaitTracked = -1;  // WAIT: the next action is a load the compiler tracks (no settle_w count)
-template <int FM_, int P2_, StepKind KIND_, unsigned OPTS_ = 0, int LM_ = kLmGeneric, int WAIT_ = kWaitTracked>
+template <int FM_, int P2_, StepKind KIND_, unsigned OPTS_ = 0, int LM_ = kLmGeneric, int WAIT_ = kWaitTracked,
+          int DEPTH_ = 2>
 struct TickCfg {
   static constexpr int FM = FM_, P2 = P2_, LM = LM_, WAIT = WAIT_;
+  static constexpr int DEPTH = DEPTH_;  // the row ring's slots (row_ring: the specialised loops; else 2)
+  static_assert(DEPTH >= 2 && DEPTH <= 4 && (DEPTH == 2 || LM_ != kLmGeneric), "row ring depth: 2..4, the fast loops only");
   static constexpr StepKind KIND = KIND_;
   static constexpr unsigned OPTS = OPTS_;
   static constexpr bool GEOM = (OPTS & kGeom) != 0, PK = (OPTS & kPacked) != 0, PF = (OPTS & kPrefetch) != 0;
@@ -1895,8 +1901,91 @@ __device__ __forceinline__ void policy_features(const Lane& L, uint32_t& d0, uin
   d1 = pack_bf16x2((float)mf * (1.0f / 55.0f), L.f.x * (1.0f / 4.6f));
 }
 
+// The wait count of settle_w in a row pipeline of `depth` slots: the vector memory ops every path
+// issues between a row's load and its wait.  Two slots: one tick's output stores, 10 per-field or
+// 2 packed, plus the next row load.  Every further slot puts one more tick's stores and load
+// (kRowOps) between the two.
+template <bool PK>
+constexpr int row_wait(int depth) {
+  constexpr int kRowWait = PK ? 3 : 11;
+  constexpr int kRowOps = PK ? 3 : 11;
+  return kRowWait + kRowOps * (depth - 2);
+}
+
+// The specialised loops' row pipeline with D = C::DEPTH > 2 slots (FS_ROW_DEPTH2; `row0` .. `row3`: rows
+// 0 .. D - 1, resident).  With two slots a row is issued 1.6 ticks before its wait, less than a first-touch
+// read from HBM takes under this kernel's stores once the tick is below ~0.85 us.
+// Here the row of tick t + D is issued at the top of tick t, into the slot tick t's row has left,
+// and tick t waits for the row of tick t + 1 with vmcnt(row_wait(D)): ticks t + 1 - D .. t - 1 issued
+// their stores and one load each behind it.  The slots are named registers and the loop is unrolled
+// by D, so no register with a load in flight is copied; the n mod D remaining ticks follow
+// step_body1's nested form (fs_arena1.h), their loads clamped to the last row.
+template <class C>
+__device__ __forceinline__ void row_ring(Lane& L, const StepParams& p, bool reads, const uint8_t* own, uint32_t row_mul,
+                                         int a, uint32_t row0, uint32_t row1, uint32_t row2, uint32_t row3) {
+  constexpr int P2 = C::P2, LM = C::LM, D = C::DEPTH;
+  constexpr bool PF = C::PF;
+  static_assert(LM != kLmGeneric && D > 2 && row_wait<C::PK>(D) <= 63, "the fast loops' ring; vmcnt has six bits");
+  using Tick = TickCfg<C::FM, P2, kRows, C::OPTS, LM, row_wait<C::PK>(D), D>;
+  L.f.won = 0;  // (inside I, and nothing in the tick sets it: not carried)
+  const int n = p.n_steps, last = n - 1;
+  const uint32_t row_step = (uint32_t)p.out_stride_steps * (uint32_t)p.n_envs;
+  const uint32_t grp = prio_group();
+  uint32_t fl[4] = {row0, row1, row2, row3};  // the slots (D of them): rows in flight, read only by their wait
+  uint32_t rd = row0;  // the row of the current tick, resident
+  Pre pre{};  // (PF: see row_loop)
+  bool have = false;
+  auto issue = [&](int t) -> uint32_t { return row_load(own + (uint32_t)min(t, last) * row_mul + (uint32_t)a); };
+  // one tick in slot J = t mod D (a compile-time index, so the slots stay in registers)
+  auto tick = [&](int t, auto J, bool use_pre) {
+    constexpr int j = decltype(J)::value, jn = (j + 1) % D;
+    fl[j] = issue(t + D);
+    if constexpr (LM == kLmFastPrio) prio_slice(grp);
+    uint32_t next = fl[jn];  // (fl[jn] itself stays the in-flight value for the final wait)
+    env_step<FS_TICK(Tick)>(L, reads ? rd & 7u : 0u, p, (uint32_t)t * row_step + (uint32_t)a, next, pre, use_pre);
+    rd = next;
+  };
+  // PF: the request of the tick that follows, from the row the tick before made resident
+  auto prepare = [&] {
+    if constexpr (PF) prepare_request<true>(L, tick_input<P2>(L, reads ? rd & 7u : 0u), pre);
+  };
+  int t = 0;
+  for (; t + D <= n; t += D) {
+    tick(t, std::integral_constant<int, 0>{}, have);
+    prepare();
+    have = PF;
+    tick(t + 1, std::integral_constant<int, 1>{}, PF);
+    prepare();
+    tick(t + 2, std::integral_constant<int, 2>{}, PF);
+    if constexpr (D > 3) {
+      prepare();
+      tick(t + 3, std::integral_constant<int, 3 % D>{}, PF);
+    }
+    if constexpr (PF) {
+      if (t + D <= last) prepare();
+    }
+  }
+  // the remaining n mod D ticks, slots 0 .. D - 2 (their waits re-read rows clamped to the last)
+  // (nested, so that no path of the code runs a later remainder tick without the earlier ones)
+  if (t < n) {
+    tick(t, std::integral_constant<int, 0>{}, have);
+    if (t + 1 < n) {
+      prepare();
+      tick(t + 1, std::integral_constant<int, 1>{}, PF);
+      if constexpr (D > 3) {
+        if (t + 2 < n) {
+          prepare();
+          tick(t + 2, std::integral_constant<int, 2>{}, PF);
+        }
+      }
+    }
+  }
+  asm volatile("s_waitcnt vmcnt(0)" ::"v"(fl[0]), "v"(fl[1]), "v"(fl[2]), "v"(fl[3]) : "memory");  // no load outlives the wave
+  L.pending = L.has_term = 0;  // (what every same-step tick leaves; n_steps > 0)
+}
+
 // The fused launches' loop over action rows (step_body; `row0` / `row1`: rows 0 and 1, issued before
-// the table staging and resident), in launch mode LM.
+// the table staging and resident), in launch mode LM.  C::DEPTH > 2: row_ring above.
 // Rows two ticks ahead, loaded and waited for as described at row_load, in two registers that swap
 // roles every tick (unrolled by two, so no register copy of a row in flight).  *_fl: a load in
 // flight (read only by its wait), *_rd: the row once resident.  A load is issued every tick (the
@@ -1905,12 +1994,10 @@ __device__ __forceinline__ void policy_features(const Lane& L, uint32_t& d0, uin
 template <class C>
 __device__ __forceinline__ void row_loop(Lane& L, const StepParams& p, bool reads, const uint8_t* own, uint32_t row_mul,
                                          int a, uint32_t row0, uint32_t row1) {
+  static_assert(C::DEPTH == 2, "deeper: row_ring");
   constexpr int P2 = C::P2, LM = C::LM;
-  constexpr bool PK = C::PK, PF = C::PF;
-  // (the wait count of settle_w: the vector memory ops every path issues between a row's load
-  // and its wait -- one tick's output stores, 10 per-field or 2 packed, plus the next row load)
-  constexpr int kRowWait = PK ? 3 : 11;
-  using Tick = TickCfg<C::FM, P2, kRows, C::OPTS, LM, kRowWait>;
+  constexpr bool PF = C::PF;
+  using Tick = TickCfg<C::FM, P2, kRows, C::OPTS, LM, row_wait<C::PK>(2)>;
   constexpr bool PRIO = LM == kLmFastPrio;
   if constexpr (LM != kLmGeneric) L.f.won = 0;  // (inside I, and nothing in the tick sets it: not carried)
   const int last = p.n_steps - 1;
@@ -1953,6 +2040,14 @@ __device__ __forceinline__ void row_loop(Lane& L, const StepParams& p, bool read
   }
   asm volatile("s_waitcnt vmcnt(0)" ::"v"(a_fl), "v"(b_fl) : "memory");  // no load outlives the wave
   if constexpr (LM != kLmGeneric) L.pending = L.has_term = 0;  // (what every same-step tick leaves; n_steps > 0)
+}
+
+// A specialised loop at its kernel's depth: two slots are row_loop's pair, more are the ring.
+template <class C>
+__device__ __forceinline__ void fast_rows(Lane& L, const StepParams& p, bool reads, const uint8_t* own, uint32_t row_mul,
+                                          int a, uint32_t row0, uint32_t row1, uint32_t row2, uint32_t row3) {
+  if constexpr (C::DEPTH > 2) row_ring<C>(L, p, reads, own, row_mul, a, row0, row1, row2, row3);
+  else row_loop<C>(L, p, reads, own, row_mul, a, row0, row1);
 }
 
 // One fused launch over all arenas (k_step_n*, the rollout: state stays in registers between the
@@ -1998,10 +2093,17 @@ __device__ __forceinline__ void step_body(const StepParams& p) {
   const uint8_t* own = reads ? src : p.p1;
   const uint32_t row_mul = reads ? (uint32_t)p.n_envs : 0u;
   auto issue = [&](int t) -> uint32_t { return row_load(own + (uint32_t)min(t, last) * row_mul + (uint32_t)a); };
-  uint32_t next, row1 = 0;
+  // (the generic loop only: general geometry and the per-arena actors, off the throughput path,
+  // and the scripted bot, whose tick has no registers to spare for a second loop's allocation)
+  constexpr bool kFastLoops = C::KIND == kRows && !(GEOM || P2 == kActors || P2 == FS_P2_BOT);
+  constexpr int D = kFastLoops ? FS_ROW_DEPTH2 : 2;  // the rows made resident before the loops part: the ring's slots
+  static_assert(D >= 2 && D <= 4, "row ring depth 2..4");
+  uint32_t next, row1 = 0, row2 = 0, row3 = 0;
   if constexpr (C::KIND == kRows) {
     next = issue(0);
     row1 = issue(1);
+    if constexpr (D > 2) row2 = issue(2);
+    if constexpr (D > 3) row3 = issue(3);
   } else {
     next = fetch(0);
   }
@@ -2047,24 +2149,24 @@ __device__ __forceinline__ void step_body(const StepParams& p) {
   } else {
     // the row loop, compiled once per launch mode (kLmFast); the choice is per wave -- no barrier
     // follows the table staging, so the waves of a block may run different loops
-    // (rows 0 and 1 made resident here, ahead of the choice: no load is in flight where the loops
-    // part and meet)
-    uint32_t row0, row1_rd;  // (early-clobber outputs: the loads' registers die here)
+    // (rows 0 .. D - 1 made resident here, ahead of the choice: no load is in flight where the loops
+    // part and meet; the generic loop starts from rows 0 and 1 and reads row 2 again)
+    uint32_t row0, row1_rd, row2_rd = 0, row3_rd = 0;  // (early-clobber outputs: the loads' registers die here)
     asm volatile("s_waitcnt vmcnt(0)\n\tv_mov_b32 %0, %2\n\tv_mov_b32 %1, %3" : "=&v"(row0), "=&v"(row1_rd)
                  : "v"(next), "v"(row1) : "memory");
+    if constexpr (D > 2) asm volatile("s_waitcnt vmcnt(0)\n\tv_mov_b32 %0, %1" : "=&v"(row2_rd) : "v"(row2) : "memory");
+    if constexpr (D > 3) asm volatile("s_waitcnt vmcnt(0)\n\tv_mov_b32 %0, %1" : "=&v"(row3_rd) : "v"(row3) : "memory");
     const bool fast = p.autoreset_mode == FS_AUTORESET_SAME_STEP && p.dense_reward &&
                       __builtin_amdgcn_ballot_w64((L.pending != 0) | !in_fast_set(L.f)) == 0;
-    using Fast = TickCfg<FM, P2, kRows, C::OPTS, kLmFast>;
-    using FastPrio = TickCfg<FM, P2, kRows, C::OPTS, kLmFastPrio>;
-    // (the generic loop only: general geometry and the per-arena actors, off the throughput path,
-    // and the scripted bot, whose tick has no registers to spare for a second loop's allocation)
-    if constexpr (GEOM || P2 == kActors || P2 == FS_P2_BOT) {
+    using Fast = TickCfg<FM, P2, kRows, C::OPTS, kLmFast, kWaitTracked, D>;
+    using FastPrio = TickCfg<FM, P2, kRows, C::OPTS, kLmFastPrio, kWaitTracked, D>;
+    if constexpr (!kFastLoops) {
       row_loop<C>(L, p, reads, own, row_mul, a, row0, row1_rd);
     } else if constexpr (PF) {  // (one wave per SIMD: no slices unless forced)
-      if (fast && !p.prio) row_loop<Fast>(L, p, reads, own, row_mul, a, row0, row1_rd);
+      if (fast && !p.prio) fast_rows<Fast>(L, p, reads, own, row_mul, a, row0, row1_rd, row2_rd, row3_rd);
       else row_loop<C>(L, p, reads, own, row_mul, a, row0, row1_rd);
     } else {  // (without slices these launches are one-tick ones, or forced: the generic loop)
-      if (fast && p.prio) row_loop<FastPrio>(L, p, reads, own, row_mul, a, row0, row1_rd);
+      if (fast && p.prio) fast_rows<FastPrio>(L, p, reads, own, row_mul, a, row0, row1_rd, row2_rd, row3_rd);
       else row_loop<C>(L, p, reads, own, row_mul, a, row0, row1_rd);
     }
   }

@@ -7,7 +7,10 @@ Each library is timed in its own subprocess (FOOTSIES_LIB override), rounds inte
 box-level drift hits every variant alike.  Per library and P2 mode (external = C3, bot = C2):
 the median duration of back-to-back fs_step_n launches (fs_step_n_packed with --packed, or per
 library with @AB_PACKED=1 / 0) of T ticks over N arenas with full trajectories, bracketed by HIP
-events on the launch stream.
+events on the launch stream.  By default every launch replays the same T action rows; with
+--fresh-rows (or @AB_FRESH=1 / 0 per library) the handle hashes T x (launches + 1) rows and every
+launch, the warm-up one included, reads T rows of its own, as bench.py's regions do.
+(A variable nothing reads, e.g. @AB_TAG=a / @AB_TAG=b, lists one library twice: the spread of one library.)
 """
 import argparse
 import os
@@ -23,27 +26,31 @@ from footsies_gym_amd import _abi
 from footsies_gym_amd._lib import check, lib
 from footsies_gym_amd.simulator import FootsiesSim
 N, T, launches = %(envs)d, %(ticks)d, %(launches)d
+fresh = int(os.environ.get("AB_FRESH", %(fresh)d))  # every launch reads action rows no launch has read before
 res = []
 for mode in ("external", "bot"):
     sim = FootsiesSim(N, p2_mode=mode, seed=0)
-    p1, p2 = sim.hash_actions(T, seed=0x5EED, p2=(mode == "external"))
+    p1, p2 = sim.hash_actions(T * (launches + 1) if fresh else T, seed=0x5EED, p2=(mode == "external"))
     q2 = C.c_void_p(p2.data_ptr()) if mode == "external" else None
+    def rows(j):  # launch j's action rows (launch 0: the warm-up)
+        off = j * T * N if fresh else 0
+        return C.c_void_p(p1.data_ptr() + off), q2 if q2 is None else C.c_void_p(p2.data_ptr() + off)
     if int(os.environ.get("AB_PACKED", %(packed)d)):  # fs_step_n_packed into packed records (the bench's layout)
         traj = sim.alloc_packed_trajectory(T)
         td = _abi.fs_packed_traj(lanes=traj["lanes"].data_ptr(), reward=traj["reward"].data_ptr(),
                                  final_lanes=traj["final_lanes"].data_ptr())
-        def run():
-            check(lib().fs_step_n_packed(sim.handle, T, C.c_void_p(p1.data_ptr()), q2, C.byref(td)), sim.handle)
+        def run(j):
+            check(lib().fs_step_n_packed(sim.handle, T, *rows(j), C.byref(td)), sim.handle)
     else:
         traj = sim.alloc_trajectory(T)
         td = _abi.fs_outputs(**{k: traj[k].data_ptr() for k in _abi.OUTPUT_SPEC})
-        def run():
-            check(lib().fs_step_n(sim.handle, T, C.c_void_p(p1.data_ptr()), q2, 0, C.byref(td)), sim.handle)
-    run(); torch.cuda.synchronize()
+        def run(j):
+            check(lib().fs_step_n(sim.handle, T, *rows(j), 0, C.byref(td)), sim.handle)
+    run(0); torch.cuda.synchronize()
     evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(launches)]
     torch.cuda._sleep(int(2e7))
-    for a, b in evs:
-        a.record(); run(); b.record()
+    for j, (a, b) in enumerate(evs):
+        a.record(); run(j + 1); b.record()
     torch.cuda.synchronize()
     d = sorted(a.elapsed_time(b) * 1e3 for a, b in evs)
     res.append(d[len(d) // 2])
@@ -77,8 +84,11 @@ def main():
     ap.add_argument("--ticks", type=int, default=1000)
     ap.add_argument("--launches", type=int, default=5)
     ap.add_argument("--packed", action="store_true", help="time fs_step_n_packed (the bench's layout)")
+    ap.add_argument("--fresh-rows", action="store_true",
+                    help="every launch reads action rows of its own (bench.py's regions) instead of replaying one set")
     a = ap.parse_args()
-    code = CODE % dict(root=ROOT, envs=a.envs, ticks=a.ticks, launches=a.launches, packed=int(a.packed))
+    code = CODE % dict(root=ROOT, envs=a.envs, ticks=a.ticks, launches=a.launches, packed=int(a.packed),
+                       fresh=int(a.fresh_rows))
     times = {lib: [] for lib in a.libs}
     for r in range(a.rounds):
         for lib in a.libs:

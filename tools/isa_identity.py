@@ -6,7 +6,10 @@
   python tools/isa_identity.py parent.s tree.s > profiles/<name>.txt
 
 A function's text runs from its first directive to the next function's: the instruction stream, the
-labels, the .amdhsa_* block and the resource comments.  One line per function: the two instruction
+labels, the .amdhsa_* block and the resource comments.  Labels an inline-asm statement numbers with
+`%=` (prio_slice's .Lprio_lo<N> / .Lprio_end<N>) count statements over the whole listing, so a kernel
+behind one that gained or lost such a statement carries other numbers around the same bytes: they are
+renumbered per function, in order of appearance, before the comparison.  One line per function: the two instruction
 counts and `identical` or `differs`.  Exit status 1 if a step kernel (k_step*) differs: a refactor
 of the tick must leave those byte for byte (DESIGN.md "The identity rule").
 """
@@ -25,7 +28,14 @@ def functions(path):
     for m, nxt in zip(starts, starts[1:] + [None]):
         out[m.group(1)] = text[m.start():nxt.start() if nxt else len(text)]
     names = subprocess.run(["c++filt"], input="\n".join(out), capture_output=True, text=True, check=True).stdout.split("\n")
-    return {re.sub(r"^void |\(.*$", "", n): t for n, t in zip(names, out.values())}
+    return {re.sub(r"^void |\(.*$", "", n): local_labels(t) for n, t in zip(names, out.values())}
+
+
+def local_labels(text):
+    """`text` with its %=-numbered inline-asm labels renumbered from 0 in order of appearance."""
+    order = {}
+    return re.sub(r"(\.L[A-Za-z_]+?)(\d+)\b(?=:|\s|$)", lambda m: m.group(0) if m.group(1).startswith((".LBB", ".Lfunc", ".Ltmp"))
+                  else "%s#%d" % (m.group(1), order.setdefault(m.group(2), len(order))), text, flags=re.M)
 
 
 def count(text):

@@ -163,10 +163,11 @@ def line_marks(src_text):
 
 def mode_loop(insts, mode):
     """[start, end] of the standard row loop of one launch mode.  A kernel with a specialised loop
-    (fs_kernels.hip kLmFast / kLmFastPrio) holds two standard row loops, each two ticks with two
-    row loads (global_load_ubyte) and no 16-byte global load (the general-geometry loop reads kRecY
-    with them); the specialised one has no pending path and none of the launch-uniform tests, so it
-    is the shorter of the two."""
+    (fs_kernels.hip kLmFast / kLmFastPrio) holds two standard row loops, each with one row load
+    (global_load_ubyte) per tick and no 16-byte global load (the general-geometry loop reads kRecY
+    with them).  The generic one is two ticks; the specialised one is unrolled by its row ring's
+    depth (row_ring, FS_ROW_DEPTH2: D ticks, D row loads), and at depth 2 it is the shorter of the
+    two: it has no pending path and none of the launch-uniform tests.  loop_ticks() counts the ticks."""
     addr = {a: i for i, (a, *_rest) in enumerate(insts)}
     loops = []
     for i, (a, mn, ops, size) in enumerate(insts):
@@ -184,9 +185,15 @@ def mode_loop(insts, mode):
     first = loops[0]
     rest = [lp for lp in loops if lp[1] < first[0] or lp[0] > first[1]]
     assert rest, "expected a generic and a specialised row loop, found one"
-    loops = sorted([first, rest[0]], key=lambda lp: lp[1] - lp[0])
-    assert all([insts[j][1] for j in range(lo, hi + 1)].count("global_load_ubyte") == 2 for lo, hi in loops), loops
+    # the generic loop: two row loads; the specialised one: more, or as many in fewer instructions
+    loops = sorted([first, rest[0]], key=lambda lp: (-loop_ticks(insts, *lp), lp[1] - lp[0]))
+    assert loop_ticks(insts, *loops[1]) == 2 and 2 <= loop_ticks(insts, *loops[0]) <= 4, loops
     return loops[0] if mode == "fast" else loops[1]
+
+
+def loop_ticks(insts, lo, hi):
+    """The ticks one iteration of a row loop holds: one row load each."""
+    return [insts[j][1] for j in range(lo, hi + 1)].count("global_load_ubyte")
 
 
 def kind(mn):
@@ -237,7 +244,8 @@ def main():
             except AssertionError:
                 a.loop = "main"
         lo, hi = IM.main_loop(insts) if a.loop == "main" else mode_loop(insts, a.loop)
-        print("loop: %s (%d instructions, two ticks)" % (a.loop, hi - lo + 1))
+        ticks = loop_ticks(insts, lo, hi) if a.loop != "main" else 2  # (main: the row loop unrolled by two)
+        print("loop: %s (%d instructions, %d ticks)" % (a.loop, hi - lo + 1, ticks))
         loop = insts[lo:hi + 1]
         n_hot = len(loop)
         if a.loop == "fast" and "wave_has_hit" in src_text:
@@ -275,8 +283,9 @@ def main():
                 if line >= first:
                     ph = p
             return ph
-        if "row_loop" in names or "step_body" in names:  # (the row loop is step_body's callee)
-            k = names.index("row_loop" if "row_loop" in names else "step_body")
+        loops = [f for f in ("row_ring", "row_loop", "step_body") if f in names]  # (step_body's callees)
+        if loops:
+            k = names.index(loops[0])
             k += 1
             while k < len(outer) and outer[k][0] == "operator()":  # (row_loop's lambdas)
                 k += 1
@@ -295,7 +304,6 @@ def main():
         if mn.startswith("v_") and not mn.startswith(("v_readfirstlane", "v_readlane", "v_writelane", "v_mfma")):
             cls[ph][IM.classify(mn, ops, size, prev_vcc)] += 1
             prev_vcc = IM.reads_vcc(mn, ops)
-    ticks = 2  # the main loop is the row loop unrolled by two ticks
     rows, common, rare, hit_only = [], collections.Counter(), collections.Counter(), collections.Counter()
     for ph, c in per.items():
         tot = sum(c.values())
@@ -320,7 +328,7 @@ def main():
            "hit_gate": gated,
            "rare_paths_per_tick_static": {k: v / ticks for k, v in sorted(rare.items())},
            "phases": rows,
-           "note": "static counts of the main loop (two ticks) / 2, charged by inline chain; rare phases run only "
+           "note": "static counts of the loop / its ticks (ticks_in_loop), charged by inline chain; rare phases run only "
                    "on waves with a hit / KO lane, and the common-path counts are the ones to compare with the "
                    "measured per-wave-tick SQ counters.  With hit_gate true the common path is the no-hit path "
                    "(no_hit_path_per_tick, the same figures), hit_path_per_tick adds the [hit] phases, which run on "

@@ -21,6 +21,8 @@ def main():
     ap.add_argument("--p2", default="external")
     ap.add_argument("--layout", choices=["fields", "packed"], default="fields",
                     help="fused mode's trajectory: one array per field (fs_step_n) or packed (fs_step_n_packed)")
+    ap.add_argument("--replay-rows", action="store_true",
+                    help="every launch reads the same action rows (tools/ab_time.py's default) instead of rows of its own")
     a = ap.parse_args()
     import torch
     from footsies_gym_amd import _abi
@@ -29,7 +31,7 @@ def main():
     N = a.envs
     sim = FootsiesSim(N, p2_mode=a.p2)
     ticks = a.chunk if a.mode == "fused" else 1
-    total = ticks * (a.launches + 2)
+    total = ticks if a.replay_rows else ticks * (a.launches + 2)
     p1, p2 = sim.hash_actions(total, seed=0x5EED)
     packed = a.mode == "fused" and a.layout == "packed"
     traj = sim.alloc_packed_trajectory(ticks) if packed else sim.alloc_trajectory(ticks)
@@ -40,7 +42,7 @@ def main():
         td = _abi.fs_outputs(**{k: traj[k].data_ptr() for k in _abi.OUTPUT_SPEC})
     h, L = sim.handle, lib()
     for j in range(a.launches + 2):
-        k = j * ticks
+        k = 0 if a.replay_rows else j * ticks
         q1 = C.c_void_p(p1.data_ptr() + k * N)
         q2 = C.c_void_p(p2.data_ptr() + k * N) if a.p2 == "external" else None
         if packed:
