@@ -43,6 +43,8 @@ FS_RECORD_BYTES = 40
 FS_KERNEL_HASHED = 1
 FS_KERNEL_POLICY = 2
 FS_KERNEL_PACKED = 4
+FS_KERNEL_SKIP_POLICY = 16
+FS_SKIP_POLICY_MAX_TICKS = 4096
 FS_PACKED_LANE_BYTES = 16
 FS_PPO_ACTOR_PARAMS = 5256
 FS_PPO_CRITIC_PARAMS = 4801
@@ -112,6 +114,10 @@ class fs_skip_out(C.Structure):
     _fields_ = [("ticks", C.c_void_p), ("pending", C.c_void_p), ("n_pending", C.c_void_p)]
 
 
+class fs_skip_traj(C.Structure):
+    _fields_ = [("ticks", C.c_void_p), ("capped", C.c_void_p)]
+
+
 class fs_policy(C.Structure):
     _fields_ = [
         ("w1", C.c_void_p), ("b1", C.c_void_p), ("w2", C.c_void_p), ("b2", C.c_void_p), ("w3", C.c_void_p),
@@ -176,6 +182,8 @@ LIB_FUNCTIONS = {
     "fs_step_n": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(fs_outputs)]),
     "fs_step_n_packed": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(fs_packed_traj)]),
     "fs_step_n_policy": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(fs_policy), C.c_void_p, C.POINTER(fs_outputs)]),
+    "fs_step_skip_policy": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(fs_policy), C.c_int, C.POINTER(fs_outputs),
+                                      C.POINTER(fs_skip_traj)]),
     "fs_ppo_workspace_bytes": (C.c_size_t, []),
     "fs_ppo_eval": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.POINTER(fs_mlp), C.POINTER(fs_mlp),
                               C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -113,6 +113,15 @@ struct SkipParams {
   int resume;            // continue the decision with input 0 from acc / nticks
 };
 
+// fs_step_skip_policy (k_step_skip_policy): one launch runs p.n_steps agent decisions per arena, the
+// actor p.pol inside; every output row is a decision's (p.pol.actions / logp, ticks_out, capped_out: [n][N])
+struct SkipPolicyParams {
+  StepParams p;         // p.n_steps: decisions; p.t0: the first decision's index (the sampling counter)
+  int32_t* ticks_out;   // [n][N] or null
+  uint8_t* capped_out;  // [n][N] or null
+  int max_ticks;        // >= 1: closes a decision
+};
+
 struct ResetParams {
   DevState st;
   DevOutputs out;
@@ -150,6 +159,8 @@ const char* step_kernel_name(bool policy, bool hashed, int n_steps, int n_envs, 
                              bool geom, bool packed, int autoreset_mode);
 // p2_mode: FS_P2_BOT or FS_P2_NOOP (the handle's fixed P2; fs_step_skip refuses the others)
 hipError_t launch_step_skip(const SkipParams& q, int float_mode, int p2_mode, hipStream_t s);
+hipError_t launch_step_skip_policy(const SkipPolicyParams& q, int float_mode, int p2_mode, hipStream_t s);
+const char* step_skip_policy_kernel_name(int float_mode, int p2_mode);
 hipError_t launch_reset(const ResetParams& p, int float_mode, hipStream_t s);
 hipError_t launch_set_p2(const DevState& st, int bot, const uint8_t* mask, int n, hipStream_t s);
 hipError_t launch_hash_actions(int n_envs, int n_steps, uint64_t seed, uint64_t t0, uint64_t arena_base, uint8_t* p1,

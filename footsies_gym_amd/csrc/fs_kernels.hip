@@ -2391,6 +2391,87 @@ __global__ __launch_bounds__(256) void k_step_skip(SkipParams q) {
   else skip_body<TickCfg<FM, P2, kHashed>>(q);
 }
 
+// fs_step_skip_policy: p.n_steps agent decisions per arena in one launch, the actor of
+// k_step_n_policy (fs_policy.h) in front of k_step_skip's loop.  The actor needs the whole wave
+// (ds_bpermute exchanges and MFMAs), so the loop is over decisions: the converged wave samples one
+// action per arena from the arena's observation as it stands, each pair then runs the tick that
+// takes it and skips on with input 0 on its own test, and the wave meets again behind the pair
+// loop -- the actor is paid once per decision, not per tick.  Lanes past the last arena stay in
+// for the actor (on a copy of arena 0 that they never tick or store), a wholly idle wave leaves.
+// `max_ticks` closes a decision (flagged in capped_out): an arena still skippable there starts an
+// ordinary decision next, so nothing but the arena state carries over between launches, and the
+// host may split a call into launches at any decision.  Row d * N + i of every output is arena
+// i's decision d: the tick's outputs of the decision's last tick (written every tick, the last
+// one's staying), `reward` the f64 sum of its ticks in order from 0.0.
+// The weight fragments are read from LDS once per decision, not held in registers across the pair
+// loop: a decision amortises the 17 reads over its ticks, and the kernel takes 234 VGPRs (bot)
+// instead of 253, three below the 256 of two waves per SIMD.
+template <class C>
+__device__ __forceinline__ void skip_policy_body(const SkipPolicyParams& q) {
+  constexpr int P2 = C::P2;
+  static_assert(C::TP == kTabLds && (P2 == FS_P2_BOT || P2 == FS_P2_NOOP), "fs_step_skip_policy: the bot or an idle P2");
+  const StepParams& p = q.p;
+  const int l = blockIdx.x * kBlock + threadIdx.x;
+  const bool active = l < 2 * p.n_envs;
+  const int a = active ? l >> 1 : 0;
+  const uint32_t k = l & 1;
+  Lane L;
+  load_lane<P2>(L, p.st, a, k);
+  if constexpr (C::GEOM) L.f.y = reinterpret_cast<const float*>(p.st.posy)[2 * a + (int)k];
+  stage_policy(p.pol);
+  stage_tables<P2 == FS_P2_BOT>();
+  if ((l & ~63) >= 2 * p.n_envs) return;  // the whole wave is past the last arena
+  L.te = next_tick_entry<false>(L.f);
+  const uint32_t row_step = (uint32_t)p.out_stride_steps * (uint32_t)p.n_envs;
+  const uint32_t arena0 = (uint32_t)(l & ~63) >> 1;
+  const uintptr_t slot = reinterpret_cast<uintptr_t>(&sSkipReward[threadIdx.x]);
+  StepParams ps = p;
+  uint32_t none = 0;
+  for (int d = 0; d < p.n_steps; d++) {
+    uint32_t d0, d1;
+    policy_features(L, d0, d1);
+    const PolicyWeights W = policy_weights();
+    const PolicyOut po = policy_act(W, d0, d1, p.pol.seed, p.arena_base + arena0, p.t0 + (uint64_t)d);
+    if (active) {
+      const uint32_t r = (uint32_t)d * row_step + (uint32_t)a;  // the decision's output row
+      // the ticks' reward row: element r is this lane's slot of LDS (skip_body)
+      uintptr_t row = slot - 8ull * r;
+      asm volatile("" : "+v"(row));
+      ps.out.reward = reinterpret_cast<double*>(row);
+      uint32_t in = po.action;
+      double acc = 0.0;
+      int ran = 0;
+      bool more;
+      do {
+        env_step<FS_TICK(C)>(L, in, ps, r, none);
+        acc += ps.out.reward[r];
+        ran++;
+        in = 0;
+        more = is_skippable(L) && !L.pending;
+      } while (more && ran < q.max_ticks);
+      if (k == 0) {
+        const uint32_t row_d = (uint32_t)d * (uint32_t)p.n_envs + (uint32_t)a;
+        p.out.reward[r] = acc;
+        if (p.pol.actions) p.pol.actions[row_d] = (uint8_t)po.action;
+        if (p.pol.logp) p.pol.logp[row_d] = po.logp;
+        if (q.ticks_out) q.ticks_out[row_d] = ran;
+        if (q.capped_out) q.capped_out[row_d] = more ? 1 : 0;
+      }
+    }
+  }
+  if (active) {
+    store_lane<P2>(L, p.st, a);
+    if constexpr (C::GEOM) reinterpret_cast<float*>(p.st.posy)[2 * a + (int)k] = L.f.y;
+  }
+}
+
+// (the general-geometry tick behind a launch-uniform branch, as in k_step_n)
+template <int FM, int P2>
+__global__ __launch_bounds__(256) void k_step_skip_policy(SkipPolicyParams q) {
+  if (q.p.geom) skip_policy_body<TickCfg<FM, P2, kHashed, kGeom>>(q);
+  else skip_policy_body<TickCfg<FM, P2, kHashed>>(q);
+}
+
 // FootsiesEnv.reset (FE:482-515) / RESET (BC:143-146) / game start (BC:105-128), every handle
 // kind through the per-arena actor logic (off the throughput path).
 template <int FM>
@@ -2816,6 +2897,26 @@ hipError_t launch_step_skip(const SkipParams& q, int float_mode, int p2_mode, hi
   if (float_mode == FS_FLOAT_DOUBLE) launch_step_skip_fm<FS_FLOAT_DOUBLE>(q, p2_mode, s);
   else launch_step_skip_fm<FS_FLOAT_STRICT32>(q, p2_mode, s);
   return hipGetLastError();
+}
+
+// (named after every other kernel, like k_step_skip above)
+template <int FM>
+static void launch_step_skip_policy_fm(const SkipPolicyParams& q, int p2_mode, hipStream_t s) {
+  const dim3 grid = grid_for(2 * q.p.n_envs), block(kBlock);
+  if (p2_mode == FS_P2_BOT) hipLaunchKernelGGL((k_step_skip_policy<FM, FS_P2_BOT>), grid, block, 0, s, q);
+  else hipLaunchKernelGGL((k_step_skip_policy<FM, FS_P2_NOOP>), grid, block, 0, s, q);
+}
+
+hipError_t launch_step_skip_policy(const SkipPolicyParams& q, int float_mode, int p2_mode, hipStream_t s) {
+  if (float_mode == FS_FLOAT_DOUBLE) launch_step_skip_policy_fm<FS_FLOAT_DOUBLE>(q, p2_mode, s);
+  else launch_step_skip_policy_fm<FS_FLOAT_STRICT32>(q, p2_mode, s);
+  return hipGetLastError();
+}
+
+const char* step_skip_policy_kernel_name(int float_mode, int p2_mode) {
+  static thread_local char buf[64];
+  snprintf(buf, sizeof buf, "fsk::k_step_skip_policy<%d, %d>", float_mode == FS_FLOAT_DOUBLE, p2_mode);
+  return buf;
 }
 
 }  // namespace fsk

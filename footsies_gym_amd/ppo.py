@@ -335,6 +335,13 @@ class PPOTrainer:
     within 5e-6 of each tensor's largest entry, as close as torch's own fp32 autograd (up to
     1.1e-5; profiles/r04e_split_error.jsonl) -- or "fp32".
 
+    `frame_skip=True` trains the way the reference does behind FootsiesFrameSkipped: `horizon` counts
+    agent decisions, each rollout is one fs_step_skip_policy launch (FusedPolicyRollout.rollout_skipped,
+    the handle's P2 the bot or idle), a sample is a decision -- its reward the sum over the ticks it
+    ran, its done the decision's `terminated`, discounting per decision -- and `stats` gains
+    `ticks_per_decision` (the mean) and `capped` (decisions closed by `max_skip_ticks`).  GAE, the
+    sample table and the learners are the same; `train` then returns decisions/s.
+
     Data-parallel (`group`: a torch.distributed process group, or "default" for the default one;
     SURVEY.md §8(e)): one trainer per rank, each over its own FootsiesSim (a ShardedSim's handle:
     its arena_base keys the actor's sampling stream, so ranks roll out different arenas), all with
@@ -347,10 +354,12 @@ class PPOTrainer:
 
     def __init__(self, sim, actor=None, critic=None, horizon=128, gamma=0.99, lam=0.95, epochs=2, minibatches=4,
                  lr=3e-4, clip=0.2, vf_coef=0.5, ent_coef=0.01, seed=0, old_logp="behaviour", learner="hip",
-                 kl_ticks=None, learner_precision="split_bf16", group=None):
+                 kl_ticks=None, learner_precision="split_bf16", group=None, frame_skip=False, max_skip_ticks=64):
         torch = _torch()
         if old_logp not in ("behaviour", "fp32"):
             raise ValueError("old_logp must be 'behaviour' or 'fp32'")
+        if frame_skip and not 1 <= int(max_skip_ticks) <= _abi.FS_SKIP_POLICY_MAX_TICKS:
+            raise ValueError("max_skip_ticks must be 1 .. %d" % _abi.FS_SKIP_POLICY_MAX_TICKS)
         if learner not in ("hip", "torch"):
             raise ValueError("learner must be 'hip' or 'torch'")
         if int(epochs) < 1 or int(minibatches) < 1 or int(horizon) < 1:
@@ -383,6 +392,10 @@ class PPOTrainer:
         n = sim.num_envs
         self.actions = torch.empty((horizon, n), dtype=torch.uint8, device=dev)
         self.logp = torch.empty((horizon, n), dtype=torch.float32, device=dev)
+        self.frame_skip, self.max_skip_ticks = bool(frame_skip), int(max_skip_ticks)
+        if self.frame_skip:  # per decision: the ticks it ran, and whether max_skip_ticks closed it
+            self.ticks = torch.empty((horizon, n), dtype=torch.int32, device=dev)
+            self.capped = torch.empty((horizon, n), dtype=torch.uint8, device=dev)
         self.gen = torch.Generator(device=dev)
         self.gen.manual_seed(seed)
         self.stats = {}
@@ -413,7 +426,11 @@ class PPOTrainer:
         as [T][N] device tensors (the trajectory's own buffers)."""
         torch = _torch()
         first = self._next_first if self._next_first is not None else obs_features(self.sim.outputs())
-        self.rollout.rollout(self.horizon, self.actions, self.logp, trajectory=self.traj)
+        if self.frame_skip:  # a row per agent decision: its last tick, the rewards of its ticks summed
+            self.rollout.rollout_skipped(self.horizon, self.actions, self.logp, self.ticks, self.capped,
+                                         trajectory=self.traj, max_ticks=self.max_skip_ticks)
+        else:
+            self.rollout.rollout(self.horizon, self.actions, self.logp, trajectory=self.traj)
         cur = torch.cuda.current_stream(self.sim.device)
         if cur != self.sim.stream:  # the trajectory was written on the handle's stream
             cur.wait_stream(self.sim.stream)
@@ -544,6 +561,9 @@ class PPOTrainer:
         self.stats = {"loss": loss.detach(), "policy_loss": pg.detach(), "value_loss": vf.detach(),
                       "entropy": ent.detach(), "mean_reward": rewards.mean(), "kl_behaviour_fp32": gap.mean(),
                       "logp_abs_diff": gap.abs().mean()}
+        if self.frame_skip:
+            self.stats["ticks_per_decision"] = self.ticks.float().mean()
+            self.stats["capped"] = self.capped.sum()
 
     def iterate(self):
         self.update(*self.collect())

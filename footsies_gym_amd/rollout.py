@@ -11,7 +11,9 @@ only the hashed-action stream and frame_delay > 0 read; use eager steps for thos
 
 :class:`FusedPolicyRollout` goes one step further: the actor runs inside the simulator's
 fused tick loop (fs_step_n_policy, csrc/fs_policy.h) as bf16 MFMAs, so a block of n
-policy-driven ticks is one kernel launch with the arena state in registers throughout.
+policy-driven ticks is one kernel launch with the arena state in registers throughout;
+``rollout_skipped`` runs n agent decisions per arena the same way (fs_step_skip_policy), the actor
+asked once per decision and each arena skipping its own frames as under FootsiesFrameSkipped.
 """
 import ctypes as C
 
@@ -125,6 +127,7 @@ class FusedPolicyRollout:
         if shapes != [(64, N_FEATURES), (64, 64), (N_ACTIONS, 64)]:
             raise ValueError("the fused actor is 8 -> 64 -> 64 -> 8; got %s" % (shapes,))
         self.sim, self.seed = sim, int(seed) & (2**64 - 1)
+        self.last_capped = None  # rollout_skipped: the last call's capped flags
         with torch.no_grad():
             self.params = [t.detach().to(device=sim.device, dtype=torch.float32).contiguous()
                            for m in lin for t in (m.weight, m.bias)]
@@ -159,3 +162,43 @@ class FusedPolicyRollout:
                                      None if p2_actions is None else C.c_void_p(p2_actions.data_ptr()),
                                      None if t is None else C.byref(t)), self.sim.handle)
         return actions, logp
+
+    def rollout_skipped(self, n, actions=None, logp=None, ticks=None, capped=None, trajectory=None,
+                        max_ticks=_abi.FS_SKIP_DEFAULT_MAX_TICKS):
+        """n agent decisions per arena in one launch (fs_step_skip_policy): the actor is asked once
+        per decision, and each arena then skips the frames in which P1 cannot act, as under the
+        reference's FootsiesFrameSkipped, its rewards summed.  Every array is [n][N] by decision:
+        `actions` (uint8) / `logp` (float32) P1's samples, `ticks` (int32) the ticks each decision
+        ran, `capped` (uint8) 1 where `max_ticks` closed a decision that was still skippable; each is
+        allocated when None, pass False to skip one.  `trajectory` rows hold each decision's last
+        tick with the summed reward.  The handle's P2 must be the bot or idle.  Returns (actions,
+        logp, ticks); the `capped` array of the call stays in ``last_capped``."""
+        n, max_ticks = int(n), int(max_ticks)
+        if n < 1:
+            raise ValueError("rollout_skipped: n must be >= 1, got %d" % n)
+        if not 1 <= max_ticks <= _abi.FS_SKIP_POLICY_MAX_TICKS:
+            raise ValueError("rollout_skipped: max_ticks must be 1 .. %d, got %d" % (_abi.FS_SKIP_POLICY_MAX_TICKS, max_ticks))
+        torch = _torch()
+        N, dev = self.sim.num_envs, self.sim.device
+        if actions is None:
+            actions = torch.empty((n, N), dtype=torch.uint8, device=dev)
+        if logp is None:
+            logp = torch.empty((n, N), dtype=torch.float32, device=dev)
+        if ticks is None:
+            ticks = torch.empty((n, N), dtype=torch.int32, device=dev)
+        if capped is None:
+            capped = torch.empty((n, N), dtype=torch.uint8, device=dev)
+        w = self.params
+        pol = _abi.fs_policy(w1=w[0].data_ptr(), b1=w[1].data_ptr(), w2=w[2].data_ptr(), b2=w[3].data_ptr(),
+                             w3=w[4].data_ptr(), b3=w[5].data_ptr(), seed=self.seed,
+                             actions_out=actions.data_ptr() if actions is not False else None,
+                             logp_out=logp.data_ptr() if logp is not False else None)
+        skip = _abi.fs_skip_traj(ticks=ticks.data_ptr() if ticks is not False else None,
+                                 capped=capped.data_ptr() if capped is not False else None)
+        t = None
+        if trajectory is not None:
+            t = _abi.fs_outputs(**{k: trajectory[k].data_ptr() for k in _abi.OUTPUT_SPEC if k in trajectory})
+        check(lib().fs_step_skip_policy(self.sim.handle, n, C.byref(pol), max_ticks,
+                                        None if t is None else C.byref(t), C.byref(skip)), self.sim.handle)
+        self.last_capped = capped
+        return actions, logp, ticks

@@ -360,6 +360,39 @@ typedef struct fs_policy {
  * FS_E_UNSUPPORTED with frame_delay > 0. */
 int fs_step_n_policy(fs_handle h, int n, const fs_policy* pol, const uint8_t* p2_act, const fs_outputs* traj);
 
+/* n agent decisions per arena in one kernel launch: fs_step_n_policy's actor in front of
+ * fs_step_skip's loop, i.e. a policy rollout under the reference's frame-skip wrapper
+ * (wrappers/frame_skip.py:46-80).  For decision d = 0 .. n-1 of arena i the actor sees the arena's
+ * observation as it stands (the handle's state at the call for d = 0, then the last tick's), draws
+ * the action with u = uniform(pol->seed, cfg.arena_base + i, fs_steps_taken + d), and the arena
+ * runs the tick that takes it, then ticks with input 0 while its observation is skippable
+ * (fs_step_skip's test) and the episode goes on.  Every tick is fs_step's.  Arenas skip their own
+ * number of ticks, and every output is indexed by decision: row d * N + i of traj receives the
+ * decision's last tick with `reward` set to the float64 sum of its ticks' rewards in tick order
+ * from 0.0 (FS_AUTORESET_SAME_STEP: final_* the terminal record of a decision that ended the
+ * episode); pol->actions_out / pol->logp_out are [n][N] per decision.  A FS_AUTORESET_NEXT_STEP
+ * arena with a reset pending runs the reset burst alone: its sampled action is recorded and
+ * ignored, ticks = 1, reward = 0.
+ *   max_ticks (1 .. FS_SKIP_POLICY_MAX_TICKS) closes a decision: an arena still skippable after
+ *     that many ticks ends the decision there (capped = 1) and its next decision is an ordinary
+ *     one, so every arena is at a decision boundary when the call returns, nothing but the arena
+ *     state carries over between calls, and a call runs at most n * max_ticks ticks.  Whenever
+ *     no decision is capped the results are the reference wrapper's on the same actions.
+ *   traj: as in fs_step_n (NULL: the handle's regular or bound outputs hold the last decision).
+ *   skip: optional, each array optional.
+ * fs_steps_taken advances by n.  Asynchronous on the handle's stream.  n * N above the
+ * trajectory row limit runs as consecutive launches (every launch ends on decision boundaries:
+ * identical results).  FS_E_UNSUPPORTED where fs_step_skip returns it (FS_P2_EXTERNAL handles,
+ * FS_P1_BOT, frame_delay > 0); FS_E_INVALID for n < 1, max_ticks out of range, a NULL pol or
+ * weight array.  (ABI 8: an addition) */
+#define FS_SKIP_POLICY_MAX_TICKS 4096
+typedef struct fs_skip_traj {
+  int32_t* ticks;   /* [n][N] device, optional: ticks each decision ran */
+  uint8_t* capped;  /* [n][N] device, optional: 1 = closed at max_ticks while still skippable */
+} fs_skip_traj;
+int fs_step_skip_policy(fs_handle h, int n, const fs_policy* pol, int max_ticks,
+                        const fs_outputs* traj, const fs_skip_traj* skip);
+
 /* The C5 learner (footsies_gym_amd/ppo.py, PPOTrainer(learner="hip")): an MLP
  * 8 -> 64 -> tanh -> 64 -> tanh -> out, fp32 device weights in torch nn.Linear layouts. */
 typedef struct fs_mlp {
@@ -543,6 +576,8 @@ uint64_t fs_steps_taken(fs_handle h);
 #define FS_KERNEL_HASHED 1
 #define FS_KERNEL_POLICY 2
 #define FS_KERNEL_PACKED 4  /* fs_step_n_packed */
+/* fs_step_skip_policy (alone; n_steps = decisions): NULL on a handle the call refuses.  (8 is not a flag.) */
+#define FS_KERNEL_SKIP_POLICY 16
 const char* fs_step_kernel(fs_handle h, int n_steps, int flags);
 void fs_destroy(fs_handle h);
 /* Last error message of h (or of the last failed fs_create when h is NULL). */

@@ -10,7 +10,8 @@ labels, the .amdhsa_* block and the resource comments.  Labels an inline-asm sta
 `%=` (prio_slice's .Lprio_lo<N> / .Lprio_end<N>) count statements over the whole listing, so a kernel
 behind one that gained or lost such a statement carries other numbers around the same bytes: they are
 renumbered per function, in order of appearance, before the comparison.  One line per function: the two instruction
-counts and `identical` or `differs`.  Exit status 1 if a step kernel (k_step*) differs: a refactor
+counts and `identical`, `differs`, or `only here` for a kernel one listing lacks (an added kernel changes
+none).  Exit status 1 if a step kernel (k_step*) of both listings differs: a refactor
 of the tick must leave those byte for byte (DESIGN.md "The identity rule").
 """
 import re
@@ -22,6 +23,10 @@ def functions(path):
     """{demangled name: text} of every function in the listing, in order."""
     text = open(path).read()
     text = text[:text.find("\t.type\t__hip_cuid_")] if "\t.type\t__hip_cuid_" in text else text
+    # (the code's end padding and the data objects follow the last function: not part of it,
+    # whichever function comes last)
+    end = re.search(r"^\t\.text\n\t\.p2alignl [^\n]*\n\t\.fill [^\n]*\n\t\.section\t\.AMDGPU\.gpr_maximums", text, re.M)
+    text = text[:end.start()] if end else text
     starts = list(re.finditer(r"^(?:\t\.section\t\.text\.\S*\n)?(?:\t\.protected\t[^\n]*\n)?\t\.globl\t(\S+)\n"
                               r"(?:\t\.p2align\t\d+\n)?\t\.type\t\1,@function\n", text, re.M))
     out = {}
@@ -48,9 +53,9 @@ def main():
     print("# %-46s %8s %8s" % ("function", "parent", "tree"))
     for name in list(a) + [n for n in b if n not in a]:
         same = a.get(name) == b.get(name)
-        bad += (not same) and name.startswith("fsk::k_step")
+        bad += (not same) and name in a and name.startswith("fsk::k_step")  # (a kernel the tree adds is no change)
         print("%-48s %8s %8s  %s" % (name, count(a[name]) if name in a else "-", count(b[name]) if name in b else "-",
-                                     "identical" if same else "differs"))
+                                     "identical" if same else "differs" if name in a and name in b else "only here"))
     steps = [n for n in a if n.startswith("fsk::k_step")]
     print("# %d functions, %d step kernels, %d step kernels differ" % (len(a), len(steps), bad))
     return 1 if bad else 0
