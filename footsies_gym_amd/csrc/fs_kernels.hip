@@ -55,6 +55,9 @@ constexpr uint32_t IN_LEFT = 1, IN_RIGHT = 2, IN_ATTACK = 4;
 // launch by all threads of the block.
 // ---------------------------------------------------------------------------
 __shared__ Tables sT;
+// The dash parser's automaton (fs_tables.h ParserTable), staged only by kernels with a specialised row
+// loop (stage_tables<.., true>): 1.7 KB beside the 35 KB image.
+__shared__ ParserTable sParser;
 
 constexpr int kBlock = 256;
 
@@ -225,6 +228,7 @@ struct InputEval {
   uint32_t held;  // bit 0 = backward held on input[0], bit 1 = forward (facing-relative)
   uint32_t atk;   // 1 = special (attack released after the charge), 2 = attack pressed, else 0
   uint32_t dash;  // 1 = forward dash, 2 = backward dash, else 0
+  uint32_t dh;    // the specialised loops' table parser only: dash << 3 | held << 1, the request index's bits
 };
 
 // Left/Right -> (bit0 = backward, bit1 = forward).  P1 faces right, P2 left for
@@ -291,6 +295,57 @@ __device__ __forceinline__ InputEval update_input(Fighter& f, uint32_t in, uint3
   const uint32_t fd = isF & ~isB & neutral & (r0 >> 1) & ~F;  // forward now, not on input[1]
   const uint32_t bd = isB & ~isF & neutral & r0 & ~B;         // backward now, not on input[1]
   e.dash = (fd & 1u) | ((bd & 1u) << 1);
+  return e;
+}
+
+// The specialised row loops (kLmFast) take the dash and the parser's next state from one read of
+// sParser instead (FS_PARSER_TABLE): what the parser reads of the history is the automaton state
+// (j, kind, run) of fs_tables.h, a function of the previous state and the tick's direction alone.  The
+// lane carries the table entry `pe` of the tick to come -- read at the end of the tick before, once
+// that tick's action row is resident (env_step), so the read is off the tick's dependent chain -- and
+// the history, which nothing in the tick reads any more, as facing-relative pairs (input[j] at bits 2j,
+// 2j + 1: one shift-or per tick), converted where the loop is entered and left.
+#ifndef FS_PARSER_TABLE
+#define FS_PARSER_TABLE 1
+#endif
+constexpr bool kParserTable = FS_PARSER_TABLE != 0;
+// rel_bits << 1 per input at a stride of four bits: a shift by (row byte << 2) -- the shifter reads five
+// bits of it, so the row byte needs no mask -- and a 3-bit extract give the entry's byte offset in its row
+constexpr uint32_t kRelLut4_0 = 0x64206420u, kRelLut4_1 = 0x62406240u;
+__device__ __forceinline__ uint32_t pairs_hist(uint32_t h) { return spread_even(h) | (spread_even(h >> 16) << 1); }
+__device__ __forceinline__ uint32_t unpair_hist(uint32_t p) { return compact_even(p) | (compact_even(p >> 1) << 16); }
+// The automaton state of a split-form history, as its row's byte offset in sParser (state * 8).  The
+// arithmetic of tools/gen_tables.py state_of, once per launch.
+__device__ __forceinline__ uint32_t parser_state_row(uint32_t h) {
+  constexpr uint32_t w = kDashAllowFrame - 1, cap = kParserRunCap;
+  static_assert(cap == w + 1 && 2 * w <= 16 && kParserStates == w * 3 * cap + 1, "the automaton of gen_tables.py");
+  const uint32_t B = h & 0xFFFFu, F = h >> 16, E = B | F;
+  const uint32_t j = (uint32_t)__builtin_ctz((E & ((1u << w) - 1u)) | (1u << w));
+  const uint32_t kind = ((B >> j) & 1u) | (((F >> j) & 1u) << 1);
+  const uint32_t run = min((uint32_t)__builtin_ctz(~(E >> j)), cap);  // (E has 16 bits: the count ends by bit 16)
+  const uint32_t s = j == w ? 0u : ((run - 1u) * w + j) * 3u + kind;
+  return s << 3;
+}
+// The entry of the tick that reads action row byte `rowb` (any value: its low three bits are the input),
+// for a lane in the state of row offset `row`.  rlut4: the lane's kRelLut4, or 0 for a lane that presses
+// nothing.
+__device__ __forceinline__ uint32_t parser_read_row(uint32_t row, uint32_t rowb, uint32_t rlut4) {
+  const uint32_t r0x2 = __builtin_amdgcn_ubfe(rlut4, rowb << 2, 3);
+  return *reinterpret_cast<const uint16_t*>(reinterpret_cast<const char*>(&sParser.next[0][0]) + (row | r0x2));
+}
+// update_input with the entry in place of the parser.  f.hist is in pairs form.
+__device__ __forceinline__ InputEval take_input(Fighter& f, uint32_t in, uint32_t pe) {
+  const int old_hold = f.hold;
+  InputEval e;
+  e.held = (pe >> 1) & 3u;
+  e.dh = pe & 0x1Eu;
+  e.dash = (pe >> 3) & 3u;
+  f.hist = (f.hist << 2) | e.held;
+  f.hold = (in & IN_ATTACK) ? min(old_hold + 1, 63) : 0;
+  const uint32_t atk_now = (in >> 2) & 1u;
+  const uint32_t held_long = ((uint32_t)(old_hold - (kSpecialHoldFrame - 1)) >> 31) ^ 1u;  // old_hold >= 59
+  const uint32_t was_up = (uint32_t)(old_hold - 1) >> 31;                                  // old_hold == 0
+  e.atk = (held_long & ~atk_now & 1u) | ((atk_now & was_up) << 1);
   return e;
 }
 
@@ -367,6 +422,10 @@ __device__ __forceinline__ uint32_t request_sel_cls(const Fighter& f, const Inpu
   const uint32_t idx = ((uint32_t)f.act << 8) | (in8 ^ (uint32_t)f.act);
   if constexpr (INV) {
     keep = early;
+    if constexpr (kParserTable) {  // (e from take_input: the dash and held bits as the entry holds them)
+      const uint32_t t8 = (((9u * cls + 3u * e.atk) << 3) + e.dh) | (uint32_t)f.prox;
+      return early ? (uint32_t)(kReqEarly + a0) : (((uint32_t)f.act << 8) | (t8 ^ (uint32_t)f.act));
+    }
     return early ? (uint32_t)(kReqEarly + a0) : idx;
   }
   keep = early | won;
@@ -773,6 +832,7 @@ __shared__ BotTables sBot;
 // four blocks per CU must fit the 160 KB of LDS: the packed launch of 262 144 arenas runs at four
 // waves per SIMD
 static_assert(sizeof(Tables) + sizeof(BotTables) <= 40 * 1024, "the staged tables: at most 40 KB per block");
+static_assert(sizeof(Tables) + sizeof(ParserTable) <= 40 * 1024, "(no kernel stages both: see step_body)");
 template <bool G>
 __device__ __forceinline__ const BotTables& bots() {
   if constexpr (G) return kBot;
@@ -798,10 +858,12 @@ __device__ __forceinline__ void lds_dma_copy(void* dst, const void* src) {
                                        (LdsPtr)(reinterpret_cast<char*>(dst) + j * 1024), 16, 0, 0);
   }
 }
-template <bool BOTS = true>
+template <bool BOTS = true, bool PARSER = false>
 __device__ __forceinline__ void stage_tables() {
+  static_assert(!(BOTS && PARSER), "the bot kernels have no specialised loop");
   lds_dma_copy<sizeof(Tables)>(&sT, &kTables);
   if constexpr (BOTS) lds_dma_copy<sizeof(BotTables)>(&sBot, &kBot);
+  if constexpr (PARSER) lds_dma_copy<sizeof(ParserTable)>(&sParser, &kParser);
   __syncthreads();  // (waits for the DMA: it counts on vmcnt)
 }
 
@@ -1020,6 +1082,8 @@ struct Lane {
   uint32_t p2bot;     // kActors: P2's actor is the bot (replica)
   AInfo ai;           // k_step only: ActionInfo of f.act
   uint32_t te;        // the fused kernels: the tick entry of (f.act, f.frame, f.stun > 0), re-read after every collision
+  uint32_t pe;        // the specialised loops: the dash parser's table entry of the tick to come (take_input)
+  uint32_t ps;        // ... and the parser state the lane is in, as its row's byte offset in sParser
   Bot bot;            // FS_P2_BOT only: this lane's queue + replicas (see Bot)
   FullBot fb;         // kActors only: this fighter's whole BattleAI
   uint4 rng;          // kActors only: the game's RNG (replica)
@@ -1331,15 +1395,16 @@ __device__ __forceinline__ void actors_request(Lane& L, const Actors& ac, float 
 //   Fight: frameCount = -1, recording index 0, state(-1) emitted, and the bots'
 //   first RequestNextInput.
 // The Intro tick of fighter k, with actor input `in`:
+template <bool PAIRS = false>  // (PAIRS: the history in the specialised loops' pairs form, see take_input)
 __device__ __forceinline__ void intro_tick(Fighter& f, uint32_t in, int k) {
   const uint32_t r = rel_bits(in, k);
-  f.hist = (r & 1) | ((r & 2) << 15);
+  f.hist = PAIRS ? r : ((r & 1) | ((r & 2) << 15));
   f.hold = (in & IN_ATTACK) ? 1 : 0;
   const bool stunned = f.stun > 0;
   f.stun -= stunned ? 1 : 0;
   f.frame = stunned ? 0 : 1;
 }
-template <int FM, int V, bool G = false>
+template <int FM, int V, bool G = false, bool PAIRS = false>
 __device__ __forceinline__ void reset_burst(Lane& L, bool after_ko, const Actors& ac) {
   constexpr bool BOT = V == FS_P2_BOT;
   if (after_ko) {
@@ -1364,7 +1429,7 @@ __device__ __forceinline__ void reset_burst(Lane& L, bool after_ko, const Actors
     L.rec = in;
     L.rec_count++;
   }
-  intro_tick(L.f, in, (int)L.k);
+  intro_tick<PAIRS>(L.f, in, (int)L.k);
   L.frame_count = -1;
   L.rec_count = 0;
   if constexpr (BOT) {
@@ -1606,6 +1671,7 @@ __device__ __forceinline__ void opaque_burst_results(Lane& L) {
   if constexpr (FLAGS)
     asm volatile("" : "+v"(L.cum), "+v"(L.pending), "+v"(L.has_term), "+v"(L.frame_count), "+v"(L.rec_count));
   else asm volatile("" : "+v"(L.cum), "+v"(L.frame_count), "+v"(L.rec_count));
+  if constexpr (!FLAGS && kParserTable) asm volatile("" : "+v"(L.ps));
 }
 
 // Tick t + 1's request inputs, prepared at the end of tick t (the fused row loop at one wave per
@@ -1629,9 +1695,31 @@ __device__ __forceinline__ uint32_t tick_input(const Lane& L, uint32_t a_own) {
   if (L.k == 0 || P2 == FS_P2_EXTERNAL) return a_own;
   return P2 == FS_P2_BOT ? L.bin : 0u;
 }
+// The table parser of the specialised loops (take_input; P2 is remote or idle there): the lane's direction
+// table -- 0 on an idle P2's lane, whose input is 0 whatever the row register holds
+// (loop-invariant: no select per tick).
+template <int P2>
+__device__ __forceinline__ uint32_t parser_rlut(uint32_t k) {
+  static_assert(P2 == FS_P2_EXTERNAL || P2 == FS_P2_NOOP, "the kernels with a specialised loop");
+  return k ? (P2 == FS_P2_NOOP ? 0u : kRelLut4_1) : kRelLut4_0;
+}
+
+// Entering a specialised loop: L.f.hist is in split form and the tick to come reads row byte `row`.
+// Leaves the history in pairs form and that tick's entry in L.pe.
+template <int P2>
+__device__ __forceinline__ void parser_enter(Lane& L, uint32_t row) {
+  L.ps = parser_state_row(L.f.hist);
+  L.pe = parser_read_row(L.ps, row, parser_rlut<P2>(L.k));
+  L.f.hist = pairs_hist(L.f.hist);
+}
+__device__ __forceinline__ void parser_leave(Lane& L) { L.f.hist = unpair_hist(L.f.hist); }
+
 template <bool INV = false>
 __device__ __forceinline__ void prepare_request(Lane& L, uint32_t in, Pre& pre) {
-  pre.e = update_input(L.f, in, L.k ? kRelLut1 : kRelLut0);
+  if constexpr (INV && kParserTable) {
+    pre.e = take_input(L.f, in, L.pe);
+    L.ps = L.pe >> 5;
+  } else pre.e = update_input(L.f, in, L.k ? kRelLut1 : kRelLut0);
   const uint32_t cls = tick_begin(L.f, L.te, &pre.rec_cont);
   bool keep;
   const uint32_t sel = request_sel_cls<INV>(L.f, pre.e, cls, keep);
@@ -1737,7 +1825,10 @@ __device__ __forceinline__ void env_step(Lane& L, uint32_t a_own, const StepPara
     rec_cont = pre.rec_cont;
     set = apply_request(L.f, pre.q, pre.keep != 0, e, &rec_set);
   } else {
-    e = update_input(L.f, in, face ? kRelLut1 : kRelLut0);
+    if constexpr (FAST && kParserTable) {
+      e = take_input(L.f, in, L.pe);
+      L.ps = L.pe >> 5;
+    } else e = update_input(L.f, in, face ? kRelLut1 : kRelLut0);
     if constexpr (G) {
       const AInfo ai = L.ai;  // ActionInfo of f.act (step_one)
       increment_action_frame(L.f, ai);
@@ -1842,7 +1933,7 @@ __device__ __forceinline__ void env_step(Lane& L, uint32_t a_own, const StepPara
       if (FAST || p.autoreset_mode == FS_AUTORESET_SAME_STEP) {
         if constexpr (PK) write_packed(L, o.pk_final, r, k == 0 ? (uint32_t)L.frame_count : 0u);
         else write_final(L, o, r);
-        reset_burst<FM, P2, G>(L, true, ac);
+        reset_burst<FM, P2, G, FAST && kParserTable>(L, true, ac);
         if constexpr (GEOM) {
           L.f.y = 0.0f;
           L.f.flip = 0;
@@ -1851,6 +1942,9 @@ __device__ __forceinline__ void env_step(Lane& L, uint32_t a_own, const StepPara
         if constexpr (!FAST) L.has_term = false;
         if constexpr (G) L.ai = stand_info();  // the burst ends on STAND
         else L.te = tick_entry(L.f);  // (STAND at frame 0 or 1, hitstun surviving)
+        // (the burst left the Intro tick's one-frame history, in pairs form: state 0, or j = 0, run = 1 of that
+        // frame's kind -- the state whose number is the frame's direction bits)
+        if constexpr (FAST && kParserTable) L.ps = L.f.hist << 3;
         // (without the pending path around the tick, this branch's join is where the burst's
         // constants would be materialized on every tick: see opaque_burst_results)
         if constexpr (FAST) opaque_burst_results<G, false>(L);
@@ -1872,6 +1966,10 @@ __device__ __forceinline__ void env_step(Lane& L, uint32_t a_own, const StepPara
       if constexpr (!FAST) L.has_term = false;
     }
   }
+  // the next tick's parser entry, from this tick's state (the burst's, after a KO) and the row
+  // that became resident at the wait above: issued here, behind the join, so the KO path only names the
+  // state; the next tick's head finds it resident behind this tick's record and stores
+  if constexpr (FAST && kParserTable) L.pe = parser_read_row(L.ps, next, parser_rlut<P2>(k));
   // (the fast loops: this record follows the same-step burst, so no DEAD / WIN remap; pk_final /
   // write_final in the KO branch above keep it)
   if constexpr (PK) {
@@ -1935,6 +2033,7 @@ __device__ __forceinline__ void row_ring(Lane& L, const StepParams& p, bool read
   uint32_t rd = row0;  // the row of the current tick, resident
   Pre pre{};  // (PF: see row_loop)
   bool have = false;
+  if constexpr (kParserTable) parser_enter<P2>(L, row0);
   auto issue = [&](int t) -> uint32_t { return row_load(own + (uint32_t)min(t, last) * row_mul + (uint32_t)a); };
   // one tick in slot J = t mod D (a compile-time index, so the slots stay in registers)
   auto tick = [&](int t, auto J, bool use_pre) {
@@ -1981,6 +2080,7 @@ __device__ __forceinline__ void row_ring(Lane& L, const StepParams& p, bool read
     }
   }
   asm volatile("s_waitcnt vmcnt(0)" ::"v"(fl[0]), "v"(fl[1]), "v"(fl[2]), "v"(fl[3]) : "memory");  // no load outlives the wave
+  if constexpr (kParserTable) parser_leave(L);  // (the history in split form again, exact)
   L.pending = L.has_term = 0;  // (what every same-step tick leaves; n_steps > 0)
 }
 
@@ -2004,6 +2104,7 @@ __device__ __forceinline__ void row_loop(Lane& L, const StepParams& p, bool read
   const uint32_t row_step = (uint32_t)p.out_stride_steps * (uint32_t)p.n_envs;
   uint32_t a_fl = row0, b_fl = row1, a_rd = row0, b_rd = row1;
   const uint32_t grp = prio_group();
+  if constexpr (LM != kLmGeneric && kParserTable) parser_enter<P2>(L, row0);
   auto slice = [&] {
     if constexpr (PRIO) prio_slice(grp);
     else if constexpr (LM == kLmGeneric) {
@@ -2039,6 +2140,7 @@ __device__ __forceinline__ void row_loop(Lane& L, const StepParams& p, bool read
     env_step<FS_TICK(Tick)>(L, reads ? a_rd & 7u : 0u, p, (uint32_t)t * row_step + (uint32_t)a, b_last, pre, have);
   }
   asm volatile("s_waitcnt vmcnt(0)" ::"v"(a_fl), "v"(b_fl) : "memory");  // no load outlives the wave
+  if constexpr (LM != kLmGeneric && kParserTable) parser_leave(L);
   if constexpr (LM != kLmGeneric) L.pending = L.has_term = 0;  // (what every same-step tick leaves; n_steps > 0)
 }
 
@@ -2108,7 +2210,7 @@ __device__ __forceinline__ void step_body(const StepParams& p) {
     next = fetch(0);
   }
   if constexpr (POL) stage_policy(p.pol);
-  stage_tables<P2 == FS_P2_BOT || P2 == kActors>();
+  stage_tables<P2 == FS_P2_BOT || P2 == kActors, kFastLoops && kParserTable>();
   if constexpr (POL) {
     if ((l & ~63) >= 2 * p.n_envs) return;  // the whole wave is past the last arena
   } else {

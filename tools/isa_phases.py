@@ -46,6 +46,10 @@ LLVM = "/opt/rocm/lib/llvm/bin"
 # function (as llvm-symbolizer --functions=short prints it, template arguments stripped) -> phase
 PHASES = {
     "update_input": "UpdateInput + dash / charge parsers (F:172-188, 569-635)",
+    "take_input": "UpdateInput + dash / charge parsers (F:172-188, 569-635)",
+    "parser_read_row": "UpdateInput + dash / charge parsers (F:172-188, 569-635)",
+    "parser_rlut": "UpdateInput + dash / charge parsers (F:172-188, 569-635)",
+    "parser_enter": "KO -> End -> Intro -> Fight burst (BC:212-345) [rare]",
     "increment_action_frame": "IncrementActionFrame (F:140-166)",
     "frame_record": "UpdateActionRequest: record index of (action, frame) (AD:87-168)",
     "request_sel": "UpdateActionRequest: request-table index (F:201-286)",
@@ -185,6 +189,9 @@ def mode_loop(insts, mode):
     first = loops[0]
     rest = [lp for lp in loops if lp[1] < first[0] or lp[0] > first[1]]
     assert rest, "expected a generic and a specialised row loop, found one"
+    # (a cold block's branch back into the ring can span more instructions than the ring's own back
+    # edge while holding fewer of its ticks: the ring is the span with the most row loads)
+    rest.sort(key=lambda lp: (-loop_ticks(insts, *lp), lp[0] - lp[1]))
     # the generic loop: two row loads; the specialised one: more, or as many in fewer instructions
     loops = sorted([first, rest[0]], key=lambda lp: (-loop_ticks(insts, *lp), lp[1] - lp[0]))
     assert loop_ticks(insts, *loops[1]) == 2 and 2 <= loop_ticks(insts, *loops[0]) <= 4, loops
