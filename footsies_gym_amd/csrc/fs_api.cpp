@@ -778,6 +778,88 @@ FS_API int fs_step_skip_policy(fs_handle h, int n, const fs_policy* pol, int max
   return FS_OK;
 }
 
+// the handles fs_step_n_selfplay refuses
+static const char* selfplay_unsupported(const fs_context* h) {
+  if (h->cfg.p2_mode != FS_P2_EXTERNAL)
+    return "the second actor plays a remote P2: the handle needs FS_P2_EXTERNAL (this one runs the in-game bot or an "
+           "idle P2)";
+  if (h->cfg.p1_mode == FS_P1_BOT) return "P1 is the bot (FS_P1_BOT), not the actor";
+  if (h->cfg.frame_delay > 0) return "the actors observe undelayed frames; frame_delay > 0 is not supported";
+  if (h->p2bot_count > 0) return "some arenas' P2 is switched to the bot (fs_set_p2_mode); switch them back first";
+  return nullptr;
+}
+
+FS_API int fs_step_n_selfplay(fs_handle h, int n, const fs_policy* p1, const fs_policy* p2, int flags,
+                              const fs_outputs* traj) {
+  if (!h) return FS_E_INVALID;
+  for (const fs_policy* pol : {p1, p2})
+    if (!pol || !pol->w1 || !pol->b1 || !pol->w2 || !pol->b2 || !pol->w3 || !pol->b3)
+      return set_err(h, FS_E_INVALID, "fs_step_n_selfplay: all six weight arrays of both actors required");
+  if (n <= 0) return set_err(h, FS_E_INVALID, "fs_step_n_selfplay: n must be > 0");
+  if (flags & ~FS_SELFPLAY_MIRROR) return set_err(h, FS_E_INVALID, "fs_step_n_selfplay: bad flags %d", flags);
+  if (const char* why = selfplay_unsupported(h)) return set_err(h, FS_E_UNSUPPORTED, "fs_step_n_selfplay: %s", why);
+  fsk::DevOutputs out = h->out;
+  if (traj) {
+    out = fsk::DevOutputs{traj->guard,          traj->move,           traj->move_frame,  traj->position,
+                          traj->reward,         traj->terminated,     traj->truncated,   traj->frame,
+                          traj->action,         traj->hitstun,        traj->final_guard, traj->final_move,
+                          traj->final_move_frame, traj->final_position, traj->final_frame, traj->final_action,
+                          traj->final_hitstun};
+    const void* req[] = {traj->guard, traj->move,   traj->move_frame, traj->position, traj->reward,
+                         traj->terminated, traj->truncated, traj->frame, traj->action, traj->hitstun};
+    for (const void* q : req)
+      if (!q) return set_err(h, FS_E_INVALID, "fs_step_n_selfplay: trajectory buffer missing");
+    if (h->cfg.autoreset_mode == FS_AUTORESET_SAME_STEP &&
+        (!traj->final_guard || !traj->final_move || !traj->final_move_frame || !traj->final_position ||
+         !traj->final_frame || !traj->final_action || !traj->final_hitstun))
+      return set_err(h, FS_E_INVALID, "fs_step_n_selfplay: final_* trajectory buffers required in same-step autoreset");
+  }
+  int rc;
+  if ((rc = use_device(h))) return rc;
+  const uint64_t N = (uint64_t)h->n;
+  uint64_t rows = kMaxLaunchRows;
+  if (const char* e = getenv("FOOTSIES_MAX_LAUNCH_ROWS"))  // (step_chunked's test hook)
+    rows = std::min<uint64_t>(rows, std::max<uint64_t>(1, strtoull(e, nullptr, 10)));
+  const int max_n = (int)std::max<uint64_t>(1, std::min<uint64_t>(rows / N, 0x7fffffff));
+  // step_chunked's split: consecutive launches over row ranges of the same buffers, both sampling
+  // streams keyed by the step counter each launch advances
+  for (int j = 0; j < n;) {
+    const int m = std::min(max_n, n - j);
+    const uint64_t row = traj ? (uint64_t)j * N : 0;  // first trajectory row of this launch
+    const uint64_t row_s = (uint64_t)j * N;           // ... of the actors' sample arrays
+    fsk::SelfPlayParams q{};
+    fsk::StepParams& sp = q.p;
+    sp.st = h->st;
+    sp.out = out;
+    auto adv = [&](auto*& p, uint64_t per_row) { if (p) p += row * per_row; };
+    adv(sp.out.guard, 2); adv(sp.out.move, 2); adv(sp.out.move_frame, 2); adv(sp.out.position, 2);
+    adv(sp.out.reward, 1); adv(sp.out.terminated, 1); adv(sp.out.truncated, 1); adv(sp.out.frame, 1);
+    adv(sp.out.action, 2); adv(sp.out.hitstun, 2); adv(sp.out.final_guard, 2); adv(sp.out.final_move, 2);
+    adv(sp.out.final_move_frame, 2); adv(sp.out.final_position, 2); adv(sp.out.final_frame, 1);
+    adv(sp.out.final_action, 2); adv(sp.out.final_hitstun, 2);
+    auto actor = [&](const fs_policy* pol) {
+      return fsk::PolicyParams{pol->w1, pol->b1, pol->w2, pol->b2, pol->w3, pol->b3,
+                               pol->actions_out ? pol->actions_out + row_s : nullptr,
+                               pol->logp_out ? pol->logp_out + row_s : nullptr, pol->seed};
+    };
+    sp.pol = actor(p1);
+    q.pol2 = actor(p2);
+    q.mirror = (flags & FS_SELFPLAY_MIRROR) != 0;
+    sp.n_envs = h->n;
+    sp.n_steps = m;
+    sp.out_stride_steps = traj ? 1 : 0;
+    sp.dense_reward = h->cfg.dense_reward;
+    sp.autoreset_mode = h->cfg.autoreset_mode;
+    sp.t0 = h->steps;
+    sp.arena_base = h->cfg.arena_base;
+    sp.geom = h->geom;
+    HIP_TRY(h, fsk::launch_step_selfplay(q, h->cfg.float_mode, h->stream));
+    h->steps += (uint64_t)m;
+    j += m;
+  }
+  return FS_OK;
+}
+
 FS_API size_t fs_ppo_workspace_bytes(void) { return fsk::ppo_workspace_bytes(); }
 
 static int ppo_grad(const float* rows, int64_t n, const fs_mlp* actor, const fs_mlp* critic, float clip,
@@ -1111,6 +1193,8 @@ FS_API int fs_set_stream(fs_handle h, void* stream) {
 FS_API const char* fs_step_kernel(fs_handle h, int n_steps, int flags) {
   if (h && n_steps > 0 && flags == FS_KERNEL_SKIP_POLICY)
     return skip_unsupported(h) ? nullptr : fsk::step_skip_policy_kernel_name(h->cfg.float_mode, h->cfg.p2_mode);
+  if (h && n_steps > 0 && flags == FS_KERNEL_SELFPLAY)
+    return selfplay_unsupported(h) ? nullptr : fsk::step_selfplay_kernel_name(h->cfg.float_mode);
   if (!h || n_steps <= 0 || (flags & ~(FS_KERNEL_HASHED | FS_KERNEL_POLICY | FS_KERNEL_PACKED))) return nullptr;
   return fsk::step_kernel_name((flags & FS_KERNEL_POLICY) != 0, (flags & FS_KERNEL_HASHED) != 0, n_steps, h->n,
                                h->cfg.float_mode, variant(h), h->geom, (flags & FS_KERNEL_PACKED) != 0,

@@ -122,6 +122,13 @@ struct SkipPolicyParams {
   int max_ticks;        // >= 1: closes a decision
 };
 
+// fs_step_n_selfplay (k_step_n_selfplay): k_step_n_policy's launch with a second actor for P2
+struct SelfPlayParams {
+  StepParams p;       // p.pol: P1's actor; p.p1 / p.p2 unused (no action rows)
+  PolicyParams pol2;  // P2's actor: its own weights, seed and [n][N] outputs
+  int mirror;         // FS_SELFPLAY_MIRROR: P2 sees the game from its own side, Left / Right exchanged
+};
+
 struct ResetParams {
   DevState st;
   DevOutputs out;
@@ -161,6 +168,9 @@ const char* step_kernel_name(bool policy, bool hashed, int n_steps, int n_envs, 
 hipError_t launch_step_skip(const SkipParams& q, int float_mode, int p2_mode, hipStream_t s);
 hipError_t launch_step_skip_policy(const SkipPolicyParams& q, int float_mode, int p2_mode, hipStream_t s);
 const char* step_skip_policy_kernel_name(int float_mode, int p2_mode);
+// (FS_P2_EXTERNAL handles with no arena switched to the bot; fs_step_n_selfplay refuses the others)
+hipError_t launch_step_selfplay(const SelfPlayParams& q, int float_mode, hipStream_t s);
+const char* step_selfplay_kernel_name(int float_mode);
 hipError_t launch_reset(const ResetParams& p, int float_mode, hipStream_t s);
 hipError_t launch_set_p2(const DevState& st, int bot, const uint8_t* mask, int n, hipStream_t s);
 hipError_t launch_hash_actions(int n_envs, int n_steps, uint64_t seed, uint64_t t0, uint64_t arena_base, uint8_t* p1,

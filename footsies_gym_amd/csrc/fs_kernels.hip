@@ -2574,6 +2574,83 @@ __global__ __launch_bounds__(256) void k_step_skip_policy(SkipPolicyParams q) {
   else skip_policy_body<TickCfg<FM, P2, kHashed>>(q);
 }
 
+// fs_step_n_selfplay: k_step_n_policy's loop (step_body, POL) with a second policy_act per tick
+// whose result is P2's input, on a handle with a remote P2.  The tick is env_step as it is; there
+// are no action rows, so nothing is in flight across it.  Both actors read the same packed
+// features of the wave: P1's as they stand, P2's either the same (q.mirror = 0: the reference hands
+// `opponent` the agent's observation, FE:526) or from P2's side (policy_act_side, mir = 1), its
+// sampled index then taking Left and Right exchanged into the game.  P2 draws with its own seed on
+// the same counter.  Lane 2a + k stores actor k's sample of arena a.
+// P1's 17 weight fragments stay in registers as in k_step_n_policy (239 VGPRs there); P2's are
+// read from a second LDS image every tick (PolicyWeightsLds): a second resident set would end two
+// waves per SIMD, which 65 536 arenas are.  Lanes past the last arena stay in for the actors, a
+// wholly idle wave leaves (as POL).
+template <class C>
+__device__ __forceinline__ void selfplay_body(const SelfPlayParams& q) {
+  constexpr int P2 = C::P2;
+  static_assert(C::TP == kTabLds && P2 == FS_P2_EXTERNAL, "fs_step_n_selfplay: a remote P2, played by the second actor");
+  const StepParams& p = q.p;
+  const int l = blockIdx.x * kBlock + threadIdx.x;
+  const bool active = l < 2 * p.n_envs;
+  const int a = active ? l >> 1 : 0;
+  const uint32_t k = l & 1;
+  Lane L;
+  load_lane<P2>(L, p.st, a, k);
+  if constexpr (C::GEOM) L.f.y = reinterpret_cast<const float*>(p.st.posy)[2 * a + (int)k];
+  stage_policy(p.pol);
+  stage_policy<true>(q.pol2, sPol2);
+  stage_tables<false>();
+  if ((l & ~63) >= 2 * p.n_envs) return;  // the whole wave is past the last arena
+  L.te = next_tick_entry<false>(L.f);
+  const uint32_t row_step = (uint32_t)p.out_stride_steps * (uint32_t)p.n_envs;
+  const uint32_t arena0 = (uint32_t)(l & ~63) >> 1;
+  const uint32_t mir = q.mirror ? 1u : 0u;
+  // this lane's actor's sample arrays (selected in registers, not per lane on the argument struct)
+  uint8_t* const act1 = p.pol.actions;
+  uint8_t* const act2 = q.pol2.actions;
+  float* const lp1 = p.pol.logp;
+  float* const lp2 = q.pol2.logp;
+  uint8_t* const act_out = k == 0 ? act1 : act2;
+  float* const logp_out = k == 0 ? lp1 : lp2;
+  uint32_t d0, d1;
+  policy_features(L, d0, d1);
+  const PolicyWeights W = policy_weights();
+  const PolicyWeightsLds W2 = policy_weights_lds(sPol2);
+  const uint32_t grp = prio_group();
+  uint32_t none = 0;
+  for (int t = 0; t < p.n_steps; t++) {
+    if (p.prio) prio_slice(grp);
+    const PolicyOut po1 = policy_act(W, d0, d1, p.pol.seed, p.arena_base + arena0, p.t0 + (uint64_t)t);
+    const PolicyOut po2 = policy_act_side(W2.fresh(), d0, d1, q.pol2.seed, p.arena_base + arena0, p.t0 + (uint64_t)t, mir);
+    if (active) {
+      const uint32_t row = (uint32_t)t * (uint32_t)p.n_envs + (uint32_t)a;
+      const uint32_t mine = k == 0 ? po1.action : po2.action;
+      if (act_out) act_out[row] = (uint8_t)mine;
+      if (logp_out) logp_out[row] = k == 0 ? po1.logp : po2.logp;
+      // P2's game input: Left (1) and Right (2) exchanged when it plays from its own side
+      const uint32_t flipped = (mine & 4u) | ((mine & 1u) << 1) | ((mine >> 1) & 1u);
+      env_step<FS_TICK(C)>(L, (k & mir) ? flipped : mine, p, (uint32_t)t * row_step + (uint32_t)a, none);
+    }
+    policy_features(L, d0, d1);
+  }
+  if (active) {
+    store_lane<P2>(L, p.st, a);
+    if constexpr (C::GEOM) reinterpret_cast<float*>(p.st.posy)[2 * a + (int)k] = L.f.y;
+  }
+}
+
+// (the general-geometry tick behind a launch-uniform branch, as in k_step_n)
+// In a namespace of its own, fsk::selfplay::k_step_n_selfplay<FM>: the kernels named fsk::k_step_n* are
+// the row / hashed / policy launches of launch_choice, a closed family that tests/test_launch_modes.py
+// counts by that prefix.
+namespace selfplay {
+template <int FM>
+__global__ __launch_bounds__(256) void k_step_n_selfplay(SelfPlayParams q) {
+  if (q.p.geom) selfplay_body<TickCfg<FM, FS_P2_EXTERNAL, kPolicy, kGeom>>(q);
+  else selfplay_body<TickCfg<FM, FS_P2_EXTERNAL, kPolicy>>(q);
+}
+}  // namespace selfplay
+
 // FootsiesEnv.reset (FE:482-515) / RESET (BC:143-146) / game start (BC:105-128), every handle
 // kind through the per-arena actor logic (off the throughput path).
 template <int FM>
@@ -3018,6 +3095,23 @@ hipError_t launch_step_skip_policy(const SkipPolicyParams& q, int float_mode, in
 const char* step_skip_policy_kernel_name(int float_mode, int p2_mode) {
   static thread_local char buf[64];
   snprintf(buf, sizeof buf, "fsk::k_step_skip_policy<%d, %d>", float_mode == FS_FLOAT_DOUBLE, p2_mode);
+  return buf;
+}
+
+// (named after every other kernel; the wave-priority slices as launch_choice sets them for k_step_n_policy)
+hipError_t launch_step_selfplay(const SelfPlayParams& q_in, int float_mode, hipStream_t s) {
+  const StepParams& p = q_in.p;
+  SelfPlayParams q = q_in;
+  q.p.prio = launch_choice(true, false, p.n_steps, p.n_envs, FS_P2_EXTERNAL, p.geom != 0, false, p.autoreset_mode).prio;
+  const dim3 grid = grid_for(2 * p.n_envs), block(kBlock);
+  if (float_mode == FS_FLOAT_DOUBLE) hipLaunchKernelGGL(selfplay::k_step_n_selfplay<FS_FLOAT_DOUBLE>, grid, block, 0, s, q);
+  else hipLaunchKernelGGL(selfplay::k_step_n_selfplay<FS_FLOAT_STRICT32>, grid, block, 0, s, q);
+  return hipGetLastError();
+}
+
+const char* step_selfplay_kernel_name(int float_mode) {
+  static thread_local char buf[64];
+  snprintf(buf, sizeof buf, "fsk::selfplay::k_step_n_selfplay<%d>", float_mode == FS_FLOAT_DOUBLE);
   return buf;
 }
 

@@ -26,6 +26,7 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 constexpr int kPolFrags = 17;  // a1[2] | a2[u=2][t,s=4] | a2b[2] | a3[4] | a3b
 constexpr int kPolA1 = 0, kPolA2 = 2, kPolA2b = 10, kPolA3 = 12, kPolA3b = 16;
 __shared__ bf16x8 sPol[kPolFrags][64];  // every wave of the block reads the same image
+__shared__ bf16x8 sPol2[kPolFrags][64];  // k_step_n_selfplay: P2's actor, read every tick (PolicyWeightsLds)
 
 __device__ __forceinline__ f32x16 mfma(bf16x8 a, bf16x8 b, f32x16 c) {
   return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
@@ -47,10 +48,13 @@ __device__ __forceinline__ void bias_pair(bf16x8& a, float b) {
   a[1] = (__bf16)(b - (float)hi);
 }
 
-// Build the weight fragments once per block (threads 0..63 write; the caller syncs).
-__device__ __forceinline__ void stage_policy(const PolicyParams& P) {
-  if (threadIdx.x >= 64) return;
-  const int l = threadIdx.x, r = l & 31, h = l >> 5;
+// Build the weight fragments once per block (threads 0..63 write; the caller syncs), into the
+// image given (the parameter shadows the global on purpose: sPol unless the caller names sPol2;
+// SECOND: the block's second wave builds it, alongside the first one's sPol).
+template <bool SECOND = false>
+__device__ __forceinline__ void stage_policy(const PolicyParams& P, bf16x8 (&sPol)[kPolFrags][64] = fsk::sPol) {
+  if (SECOND ? (threadIdx.x < 64 || threadIdx.x >= 128) : threadIdx.x >= 64) return;
+  const int l = SECOND ? threadIdx.x - 64 : threadIdx.x, r = l & 31, h = l >> 5;
   for (int t = 0; t < 2; t++) {  // layer 1: row = hidden 32t + r; k = feature 8h + j, bias at k = 8, 9
     bf16x8 a = {};
     const int row = 32 * t + r;
@@ -138,6 +142,7 @@ struct PolicyOut {
 // per wave-tick less on the LDS pipe and none on the MFMA's operand path.
 struct PolicyWeights {
   bf16x8 f[kPolFrags];
+  __device__ __forceinline__ bf16x8 frag(int i) const { return f[i]; }
 };
 __device__ __forceinline__ PolicyWeights policy_weights() {
   PolicyWeights w;
@@ -147,12 +152,36 @@ __device__ __forceinline__ PolicyWeights policy_weights() {
   return w;
 }
 
-__device__ __forceinline__ PolicyOut policy_act(const PolicyWeights& W, uint32_t d0, uint32_t d1, uint64_t seed,
-                                                uint64_t arena0, uint64_t t) {
+// The same fragments left in LDS (`img`: sPol2, staged by stage_policy) and read where the actor uses
+// them, for a second actor in a kernel whose registers hold the first one's.  fresh() once per tick:
+// the address goes through an opaque copy, so the 17 reads stay inside the tick loop instead of
+// becoming 68 more loop-carried registers.
+struct PolicyWeightsLds {
+  typedef const bf16x8 __attribute__((address_space(3))) * Ptr;
+  uint32_t at;  // LDS byte address of img[0][lane]
+  __device__ __forceinline__ bf16x8 frag(int i) const { return ((Ptr)(uintptr_t)at)[64 * i]; }
+  __device__ __forceinline__ PolicyWeightsLds fresh() const {
+    PolicyWeightsLds w = *this;
+    asm volatile("" : "+v"(w.at));
+    return w;
+  }
+};
+__device__ __forceinline__ PolicyWeightsLds policy_weights_lds(bf16x8 (&img)[kPolFrags][64]) {
+  return {(uint32_t)(uintptr_t)(PolicyWeightsLds::Ptr)&img[0][threadIdx.x & 63]};
+}
+
+// policy_act below for either side.  mir = 0: the observation as P1 sees it.  mir = 1
+// (FS_SELFPLAY_MIRROR, wave-uniform): the game from P2's side -- each feature pair swapped (the
+// gather takes pair lane 2r + 1 first) and both positions negated (the sign bits of the two bf16
+// positions); the arithmetic is the same.
+template <class WS>
+__device__ __forceinline__ PolicyOut policy_act_side(const WS& W, uint32_t d0, uint32_t d1, uint64_t seed,
+                                                     uint64_t arena0, uint64_t t, uint32_t mir) {
   const int l = threadIdx.x & 63, r = l & 31, h = l >> 5;
   // gather: MFMA lane r takes arena r's two fighters (pair lanes 2r, 2r + 1)
-  const uint32_t p1d0 = lane_read(d0, 2 * r), p2d0 = lane_read(d0, 2 * r + 1);
-  const uint32_t p1d1 = lane_read(d1, 2 * r), p2d1 = lane_read(d1, 2 * r + 1);
+  const int own = (2 * r) ^ (int)mir, opp = (2 * r + 1) ^ (int)mir;
+  const uint32_t p1d0 = lane_read(d0, own), p2d0 = lane_read(d0, opp);
+  const uint32_t p1d1 = lane_read(d1, own), p2d1 = lane_read(d1, opp);
   bf16x8 x;
   {
     typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
@@ -161,7 +190,7 @@ __device__ __forceinline__ PolicyOut policy_act(const PolicyWeights& W, uint32_t
     v.x = __builtin_amdgcn_perm(p2d0, p1d0, 0x05040100u);  // lo halves: g1 | g2
     v.y = __builtin_amdgcn_perm(p2d0, p1d0, 0x07060302u);  // hi halves: m1 | m2
     v.z = __builtin_amdgcn_perm(p2d1, p1d1, 0x05040100u);
-    v.w = __builtin_amdgcn_perm(p2d1, p1d1, 0x07060302u);
+    v.w = __builtin_amdgcn_perm(p2d1, p1d1, 0x07060302u) ^ (mir ? 0x80008000u : 0u);
     const u32x4 one = {0x3F803F80u, 0u, 0u, 0u};  // k = 8, 9: bf16 1.0 (the layer-1 bias pair)
     x = __builtin_bit_cast(bf16x8, h == 0 ? v : one);
   }
@@ -169,7 +198,7 @@ __device__ __forceinline__ PolicyOut policy_act(const PolicyWeights& W, uint32_t
   if (h == 0) ones[0] = ones[1] = (__bf16)1.0f;
   const f32x16 zero = {};
   // layer 1
-  f32x16 d1a = mfma(W.f[kPolA1 + 0], x, zero), d1b = mfma(W.f[kPolA1 + 1], x, zero);
+  f32x16 d1a = mfma(W.frag(kPolA1 + 0), x, zero), d1b = mfma(W.frag(kPolA1 + 1), x, zero);
   bf16x8 h1[2][2];
   activate(d1a, h1[0][0], h1[0][1]);
   activate(d1b, h1[1][0], h1[1][1]);
@@ -177,19 +206,19 @@ __device__ __forceinline__ PolicyOut policy_act(const PolicyWeights& W, uint32_t
   bf16x8 h2[2][2];
 #pragma unroll
   for (int u = 0; u < 2; u++) {
-    f32x16 acc = mfma(W.f[kPolA2b + u], ones, zero);
+    f32x16 acc = mfma(W.frag(kPolA2b + u), ones, zero);
 #pragma unroll
     for (int tt = 0; tt < 2; tt++)
 #pragma unroll
-      for (int s = 0; s < 2; s++) acc = mfma(W.f[kPolA2 + 4 * u + 2 * tt + s], h1[tt][s], acc);
+      for (int s = 0; s < 2; s++) acc = mfma(W.frag(kPolA2 + 4 * u + 2 * tt + s), h1[tt][s], acc);
     activate(acc, h2[u][0], h2[u][1]);
   }
   // layer 3: logits of actions 4h .. 4h + 3 land in registers 0..3
-  f32x16 lg = mfma(W.f[kPolA3b], ones, zero);
+  f32x16 lg = mfma(W.frag(kPolA3b), ones, zero);
 #pragma unroll
   for (int u = 0; u < 2; u++)
 #pragma unroll
-    for (int s = 0; s < 2; s++) lg = mfma(W.f[kPolA3 + 2 * u + s], h2[u][s], lg);
+    for (int s = 0; s < 2; s++) lg = mfma(W.frag(kPolA3 + 2 * u + s), h2[u][s], lg);
   // softmax over the two halves (partner lane l ^ 32), inverse-CDF sample, log-probability
   const float m_mine = fmaxf(fmaxf(lg[0], lg[1]), fmaxf(lg[2], lg[3]));
   const float m = fmaxf(m_mine, lane_read(m_mine, l ^ 32));
@@ -216,6 +245,11 @@ __device__ __forceinline__ PolicyOut policy_act(const PolicyWeights& W, uint32_t
   o.action = lane_read(action, l >> 1);
   o.logp = lane_read(chosen - m - __logf(total), l >> 1);
   return o;
+}
+
+__device__ __forceinline__ PolicyOut policy_act(const PolicyWeights& W, uint32_t d0, uint32_t d1, uint64_t seed,
+                                                uint64_t arena0, uint64_t t) {
+  return policy_act_side(W, d0, d1, seed, arena0, t, 0u);
 }
 
 }  // namespace fsk

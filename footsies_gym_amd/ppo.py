@@ -33,7 +33,7 @@ import time
 
 from . import _abi
 from ._lib import check, lib
-from .rollout import N_ACTIONS, N_FEATURES, FusedPolicyRollout, make_actor, obs_features
+from .rollout import N_ACTIONS, N_FEATURES, FusedPolicyRollout, FusedSelfPlayRollout, make_actor, obs_features
 
 
 def _torch():
@@ -342,6 +342,13 @@ class PPOTrainer:
     `ticks_per_decision` (the mean) and `capped` (decisions closed by `max_skip_ticks`).  GAE, the
     sample table and the learners are the same; `train` then returns decisions/s.
 
+    `self_play=True` (a sim created with p2_mode="external"; not with `frame_skip`): P1 learns exactly
+    as above while P2 plays a frozen, mirrored copy of the actor inside the same launch
+    (FusedSelfPlayRollout, fs_step_n_selfplay; `opponent_seed` is its sampling seed).  The copy is
+    re-taken from the learner after every `opponent_refresh`-th update (1: always the latest policy),
+    and `stats["opponent_age"]` holds the updates since.  P2's samples are not learnt from.
+    Data-parallel ranks hold identical weights and refresh at the same update.
+
     Data-parallel (`group`: a torch.distributed process group, or "default" for the default one;
     SURVEY.md §8(e)): one trainer per rank, each over its own FootsiesSim (a ShardedSim's handle:
     its arena_base keys the actor's sampling stream, so ranks roll out different arenas), all with
@@ -354,8 +361,16 @@ class PPOTrainer:
 
     def __init__(self, sim, actor=None, critic=None, horizon=128, gamma=0.99, lam=0.95, epochs=2, minibatches=4,
                  lr=3e-4, clip=0.2, vf_coef=0.5, ent_coef=0.01, seed=0, old_logp="behaviour", learner="hip",
-                 kl_ticks=None, learner_precision="split_bf16", group=None, frame_skip=False, max_skip_ticks=64):
+                 kl_ticks=None, learner_precision="split_bf16", group=None, frame_skip=False, max_skip_ticks=64,
+                 self_play=False, opponent_refresh=1, opponent_seed=None):
         torch = _torch()
+        if self_play and sim.p2_mode != "external":
+            raise ValueError("self_play needs a sim created with p2_mode='external' (the second actor plays P2), "
+                             "got %r" % (sim.p2_mode,))
+        if self_play and frame_skip:
+            raise ValueError("self_play with frame_skip=True is not built (fs_step_skip_policy has no second actor)")
+        if self_play and int(opponent_refresh) < 1:
+            raise ValueError("opponent_refresh must be >= 1, got %r" % (opponent_refresh,))
         if old_logp not in ("behaviour", "fp32"):
             raise ValueError("old_logp must be 'behaviour' or 'fp32'")
         if frame_skip and not 1 <= int(max_skip_ticks) <= _abi.FS_SKIP_POLICY_MAX_TICKS:
@@ -377,7 +392,12 @@ class PPOTrainer:
             self.world = dist.get_world_size(self.group)
         if self.world > 1:
             self._join_ranks(sim.num_envs)
-        self.rollout = FusedPolicyRollout(sim, self.actor, seed=seed)
+        self.self_play, self.opponent_refresh = bool(self_play), int(opponent_refresh)
+        self._updates = self._opponent_taken = 0  # updates done; the count at which the opponent was copied
+        if self.self_play:  # (opponent=None: a copy of the actor as it is now)
+            self.rollout = FusedSelfPlayRollout(sim, self.actor, seed=seed, opponent_seed=opponent_seed, mirror=True)
+        else:
+            self.rollout = FusedPolicyRollout(sim, self.actor, seed=seed)
         self.horizon, self.gamma, self.lam = horizon, gamma, lam
         # the fp32 log-probs behind kl_behaviour_fp32 / logp_abs_diff: every tick when they are
         # PPO's old log-probs, else a sample of the first `kl_ticks` ticks (all arenas)
@@ -429,6 +449,8 @@ class PPOTrainer:
         if self.frame_skip:  # a row per agent decision: its last tick, the rewards of its ticks summed
             self.rollout.rollout_skipped(self.horizon, self.actions, self.logp, self.ticks, self.capped,
                                          trajectory=self.traj, max_ticks=self.max_skip_ticks)
+        elif self.self_play:  # P2's samples are not learnt from: not stored
+            self.rollout.rollout(self.horizon, self.actions, self.logp, False, False, trajectory=self.traj)
         else:
             self.rollout.rollout(self.horizon, self.actions, self.logp, trajectory=self.traj)
         cur = torch.cuda.current_stream(self.sim.device)
@@ -550,6 +572,10 @@ class PPOTrainer:
                 self._average_grads()
                 self.opt.step()
         self.rollout.refresh(self.actor)
+        self._updates += 1
+        if self.self_play and self._updates % self.opponent_refresh == 0:  # (every rank at the same update)
+            self.rollout.refresh_opponent(self.actor)
+            self._opponent_taken = self._updates
         if self._grad is not None:
             pg, vf, ent = lm[0].clone(), lm[1].clone(), lm[2].clone()
             loss = pg + self.vf_coef * vf - self.ent_coef * ent
@@ -564,6 +590,8 @@ class PPOTrainer:
         if self.frame_skip:
             self.stats["ticks_per_decision"] = self.ticks.float().mean()
             self.stats["capped"] = self.capped.sum()
+        if self.self_play:  # updates since the opponent's weights were copied from the learner
+            self.stats["opponent_age"] = torch.tensor(self._updates - self._opponent_taken)
 
     def iterate(self):
         self.update(*self.collect())

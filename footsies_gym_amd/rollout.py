@@ -14,6 +14,9 @@ fused tick loop (fs_step_n_policy, csrc/fs_policy.h) as bf16 MFMAs, so a block o
 policy-driven ticks is one kernel launch with the arena state in registers throughout;
 ``rollout_skipped`` runs n agent decisions per arena the same way (fs_step_skip_policy), the actor
 asked once per decision and each arena skipping its own frames as under FootsiesFrameSkipped.
+
+:class:`FusedSelfPlayRollout` adds a second in-kernel actor for P2 (fs_step_n_selfplay): self-play,
+or any learned opponent of the same shape, with both fighters reacting every tick inside one launch.
 """
 import ctypes as C
 
@@ -202,3 +205,81 @@ class FusedPolicyRollout:
                                         None if t is None else C.byref(t), C.byref(skip)), self.sim.handle)
         self.last_capped = capped
         return actions, logp, ticks
+
+
+def mirror_features(x):
+    """The [..., 8] feature rows of obs_features as P2 sees the game from its own side
+    (FS_SELFPLAY_MIRROR): each pair swapped and both positions negated,
+    g2, g1, m2, m1, mf2, mf1, -x2, -x1.  numpy array or torch tensor; its own inverse."""
+    y = x[..., [1, 0, 3, 2, 5, 4, 7, 6]]
+    y[..., 6:] = -y[..., 6:]  # (the fancy index above made a copy)
+    return y
+
+
+def swap_left_right(a):
+    """Action indices (Left = 1, Right = 2, Attack = 4) with Left and Right exchanged: the game
+    input of a mirrored P2 actor's sampled index.  numpy array, torch tensor or int; its own inverse."""
+    return (a & 4) | ((a & 1) << 1) | ((a >> 1) & 1)
+
+
+class FusedSelfPlayRollout(FusedPolicyRollout):
+    """Self-play in one launch per block of ticks (fs_step_n_selfplay): `actor` plays P1 as in
+    FusedPolicyRollout and a second in-kernel actor, `opponent`, plays P2 of a handle created with
+    p2_mode="external", reacting to the game every tick.  `opponent=None` takes a copy of
+    `actor`'s weights (refresh_opponent re-takes it).  With `mirror` the opponent sees the game from
+    its own side (mirror_features) and its sampled index reaches the game with Left and Right
+    exchanged (swap_left_right), so one set of weights plays either side; without it the opponent
+    receives P1's observation and its index is P2's input as is, which is what the reference hands
+    a custom `opponent` policy.  `opponent_seed=None` derives a seed different from `seed`: with
+    equal weights, equal seeds and `mirror` both fighters would act identically for as long as the
+    game stays symmetric."""
+
+    def __init__(self, sim, actor, opponent=None, seed=0, opponent_seed=None, mirror=True):
+        super().__init__(sim, actor, seed=seed)
+        # (cloned: `params` may be the module's own tensors when it already sits on the device in fp32,
+        # and the opponent has to stay what it was while the learner moves on)
+        self.params2 = [p.clone() for p in FusedPolicyRollout(sim, actor if opponent is None else opponent).params]
+        if opponent_seed is None:
+            opponent_seed = self.seed ^ 0x9E3779B97F4A7C15  # (never equal to seed)
+        self.opponent_seed = int(opponent_seed) & (2**64 - 1)
+        self.mirror = bool(mirror)
+
+    def refresh_opponent(self, actor):
+        """Copy new weights into the opponent's buffers, which stay put."""
+        torch = _torch()
+        lin = [m for m in actor if isinstance(m, torch.nn.Linear)]
+        with torch.no_grad():
+            for dst, src in zip(self.params2, [t for m in lin for t in (m.weight, m.bias)]):
+                dst.copy_(src)
+
+    def rollout(self, n, actions=None, logp=None, p2_actions=None, p2_logp=None, trajectory=None):
+        """n ticks in one launch, both fighters sampled in-kernel.  `actions` / `logp` receive P1's
+        samples, `p2_actions` / `p2_logp` P2's (its sampled index, before swap_left_right; [n][N]
+        uint8 / float32 device tensors, allocated when None; pass False to skip one).  Rewards and
+        `trajectory` are P1's, as in FusedPolicyRollout.  Returns (actions, logp, p2_actions, p2_logp)."""
+        torch = _torch()
+        N, dev = self.sim.num_envs, self.sim.device
+        n = int(n)
+        out = []
+        for given, dtype in ((actions, torch.uint8), (logp, torch.float32), (p2_actions, torch.uint8),
+                             (p2_logp, torch.float32)):
+            out.append(torch.empty((n, N), dtype=dtype, device=dev) if given is None else given)
+
+        def actor(w, seed, a, lp):
+            return _abi.fs_policy(w1=w[0].data_ptr(), b1=w[1].data_ptr(), w2=w[2].data_ptr(), b2=w[3].data_ptr(),
+                                  w3=w[4].data_ptr(), b3=w[5].data_ptr(), seed=seed,
+                                  actions_out=a.data_ptr() if a is not False else None,
+                                  logp_out=lp.data_ptr() if lp is not False else None)
+        p1 = actor(self.params, self.seed, out[0], out[1])
+        p2 = actor(self.params2, self.opponent_seed, out[2], out[3])
+        t = None
+        if trajectory is not None:
+            t = _abi.fs_outputs(**{k: trajectory[k].data_ptr() for k in _abi.OUTPUT_SPEC if k in trajectory})
+        check(lib().fs_step_n_selfplay(self.sim.handle, n, C.byref(p1), C.byref(p2),
+                                       _abi.FS_SELFPLAY_MIRROR if self.mirror else 0,
+                                       None if t is None else C.byref(t)), self.sim.handle)
+        return tuple(out)
+
+    def rollout_skipped(self, *args, **kwargs):
+        raise NotImplementedError("self-play per agent decision is not built: P2 would have to act inside P1's "
+                                  "skipped frames (fs_step_skip_policy has no second actor)")

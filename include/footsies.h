@@ -393,6 +393,29 @@ typedef struct fs_skip_traj {
 int fs_step_skip_policy(fs_handle h, int n, const fs_policy* pol, int max_ticks,
                         const fs_outputs* traj, const fs_skip_traj* skip);
 
+/* Self-play in one launch: fs_step_n_policy with a second in-kernel actor playing P2, so the
+ * opponent reacts to the game every tick (the reference's custom `opponent` policy, FE:47, 119,
+ * 525-527, on the fused path).  Every tick is fs_step's with P1's input sampled from p1 and P2's
+ * from p2; reward, traj and the regular outputs are fs_step_n_policy's (the reward is P1's).
+ *   p1, p2: both actors in full (six weight arrays each).  p2->seed is P2's own sampling seed:
+ *     u = uniform(p2->seed, cfg.arena_base + i, fs_steps_taken + k), the function and counter of
+ *     P1's draw.  p2->actions_out / p2->logp_out ([n][N] device, optional) receive P2's sampled
+ *     index -- before the Left/Right exchange below -- and its log-probability.
+ *   flags = 0: P2's actor sees P1's observation (g1, g2, m1, m2, mf1, mf2, x1, x2), which is what
+ *     the reference hands `opponent(obs, info)` (FE:526), and its sampled index is P2's input.
+ *   flags = FS_SELFPLAY_MIRROR: P2's actor sees the game from its own side -- each feature pair
+ *     swapped and both positions negated (g2, g1, m2, m1, mf2, mf1, -x2, -x1) -- and P2's input is
+ *     its sampled index a with Left (1) and Right (2) exchanged, (a & 4) | ((a & 1) << 1) |
+ *     ((a >> 1) & 1): one set of weights plays either side.
+ * fs_steps_taken advances by n.  Asynchronous on the handle's stream; n * N above the trajectory
+ * row limit runs as consecutive launches with identical results.  FS_E_UNSUPPORTED unless the
+ * handle's P2 is FS_P2_EXTERNAL with no arena switched to the bot (fs_set_p2_mode), P1 is the agent
+ * and frame_delay is 0; FS_E_INVALID for n <= 0, unknown flag bits, a NULL actor or weight array,
+ * or trajectory buffers fs_step_n_policy would refuse.  (ABI 8: an addition) */
+#define FS_SELFPLAY_MIRROR 1
+int fs_step_n_selfplay(fs_handle h, int n, const fs_policy* p1, const fs_policy* p2, int flags,
+                       const fs_outputs* traj);
+
 /* The C5 learner (footsies_gym_amd/ppo.py, PPOTrainer(learner="hip")): an MLP
  * 8 -> 64 -> tanh -> 64 -> tanh -> out, fp32 device weights in torch nn.Linear layouts. */
 typedef struct fs_mlp {
@@ -578,6 +601,8 @@ uint64_t fs_steps_taken(fs_handle h);
 #define FS_KERNEL_PACKED 4  /* fs_step_n_packed */
 /* fs_step_skip_policy (alone; n_steps = decisions): NULL on a handle the call refuses.  (8 is not a flag.) */
 #define FS_KERNEL_SKIP_POLICY 16
+/* fs_step_n_selfplay (alone; "fsk::selfplay::k_step_n_selfplay<0>"): NULL on a handle the call refuses */
+#define FS_KERNEL_SELFPLAY 32
 const char* fs_step_kernel(fs_handle h, int n_steps, int flags);
 void fs_destroy(fs_handle h);
 /* Last error message of h (or of the last failed fs_create when h is NULL). */
