@@ -64,7 +64,7 @@ struct fs_context {
   uint8_t* h_mask = nullptr;     // pinned [N]
   hipEvent_t staging_free = nullptr;
   uint4* delay_ring = nullptr;   // frame_delay > 0: [d][N] x 32-B observation records (fs_delay.hip)
-  uint8_t* delay_head = nullptr; // frame_delay > 0: [N] each arena's ring head
+  uint16_t* delay_head = nullptr; // frame_delay > 0: [N] each arena's ring head
   double* skip_acc = nullptr;    // fs_step_skip: [N] each arena's reward sum of its current decision
   int32_t* skip_ticks = nullptr; // fs_step_skip: [N] each arena's tick count of its current decision
   std::vector<uint8_t> p2bot;    // host mirror of each arena's P2 actor (1 = the bot)
@@ -310,7 +310,7 @@ FS_API int fs_create(const fs_config* cfg, fs_handle* out) {
   if (cfg->frame_delay > 0 && ((rc = dalloc(h, &h->delay_ring, 2 * (size_t)cfg->frame_delay * N)) ||
                                (rc = dalloc(h, &h->delay_head, N))))
     return fail(rc);
-  if (cfg->frame_delay > 0 && hipMemsetAsync(h->delay_head, 0, N, h->stream) != hipSuccess)
+  if (cfg->frame_delay > 0 && hipMemsetAsync(h->delay_head, 0, N * sizeof(uint16_t), h->stream) != hipSuccess)
     return fail(set_err(h, FS_E_DEVICE, "memset"));
   if (hipHostMalloc((void**)&h->h_act, 2 * N, hipHostMallocDefault) != hipSuccess ||
       hipHostMalloc((void**)&h->h_seeds, N * sizeof(uint64_t), hipHostMallocDefault) != hipSuccess ||
@@ -375,7 +375,9 @@ FS_API int fs_reset(fs_handle h, const uint64_t* seeds, const uint8_t* mask, int
   }
   HIP_TRY(h, hipEventRecord(h->staging_free, h->stream));
   HIP_TRY(h, fsk::launch_reset(rp, h->cfg.float_mode, h->stream));
-  if (flags != FS_RESET_SEED_ONLY && (rc = apply_delay(h, h->out, 1, 0, true))) return rc;
+  // the queues of the arenas this call reset, and of no other: an arena outside the mask may still
+  // show a delayed copy of state(-1) in its row, with real frames queued behind it
+  if (flags != FS_RESET_SEED_ONLY && (rc = apply_delay(h, h->out, 1, 0, true, rp.mask))) return rc;
   return FS_OK;
 }
 

@@ -21,6 +21,8 @@
 
 namespace fsk {
 
+static_assert(FS_MAX_FRAME_DELAY - 1 <= 0xFFFF, "DelayParams::head holds slots up to FS_MAX_FRAME_DELAY - 1");
+
 namespace {
 
 struct Rec {
@@ -75,7 +77,7 @@ __global__ __launch_bounds__(256) void k_delay(DelayParams p) {
   if (a >= p.n_envs) return;
   const uint32_t N = (uint32_t)p.n_envs;
   const uint32_t row_step = (uint32_t)p.out_stride_steps * N;
-  if (p.active && !p.active[a]) return;  // an idle arena: no row, no shift
+  if (p.active && !p.active[a]) return;  // an idle arena: no row, no shift (a masked reset: not reset, no refill)
   auto slot_ptr = [&](uint32_t slot) { return p.ring + 2 * ((size_t)slot * N + (uint32_t)a); };
   uint32_t slot = p.head[a];
   for (int t = 0; t < p.n_steps; t++) {
@@ -100,7 +102,7 @@ __global__ __launch_bounds__(256) void k_delay(DelayParams p) {
     }
     slot = slot + 1 == (uint32_t)p.delay ? 0u : slot + 1;  // (a refill leaves every slot equal)
   }
-  if (!p.refill_only) p.head[a] = (uint8_t)slot;
+  if (!p.refill_only) p.head[a] = (uint16_t)slot;
 }
 
 }  // namespace

@@ -143,9 +143,9 @@ struct ResetParams {
 };
 
 // FootsiesEnv's delayed-frame queue (FE:126-131, 493-504, 532-535) for frame_delay = d > 0:
-// per arena a ring of d packed observation records, slot = global step index mod d
-// (all arenas step together).  Applied after a step kernel to the rows it wrote, or
-// after a reset to refill the rings of fresh arenas (output frame == -1).
+// per arena a ring of d packed observation records and a head slot that advances with the
+// arena's own steps.  Applied after a step kernel to the rows it wrote, or after a reset to
+// refill the rings of the arenas it reset (output frame == -1).
 struct DelayParams {
   DevOutputs out;
   uint4* ring;          // [d][N] records of 2 x uint4 (layout in fs_delay.hip)
@@ -153,8 +153,8 @@ struct DelayParams {
   int delay;            // d
   int n_steps;          // rows to process (1 for fs_step / fs_reset)
   int out_stride_steps;
-  uint8_t* head;        // [N] per arena: the ring slot its next step reads and overwrites
-  const uint8_t* active;  // fs_step_masked: only these arenas stepped (nullptr = all)
+  uint16_t* head;       // [N] per arena: the ring slot its next step reads and overwrites (< d)
+  const uint8_t* active;  // fs_step_masked / a masked fs_reset: only these arenas stepped / were reset (nullptr = all)
   int refill_only;      // 1: after fs_reset / fs_create (no queue shift)
   int same_step;        // FS_AUTORESET_SAME_STEP: a terminal row's final_* take the delayed record
 };

@@ -6,7 +6,7 @@ import numpy as np
 from footsies_gym_amd import _abi
 from footsies_gym_amd import spaces as sp
 from footsies_gym_amd.simulator import encode_actions
-from footsies_gym_amd.vector_env import obs_info_from_outputs, step_result_from_outputs
+from footsies_gym_amd.vector_env import obs_info_from_outputs, reset_seeds, step_result_from_outputs
 
 AR = {"same_step": _abi.FS_AUTORESET_SAME_STEP, "next_step": _abi.FS_AUTORESET_NEXT_STEP}
 
@@ -24,7 +24,13 @@ class OracleVectorEnv:
         return {k: np.array(v, copy=True) for k, v in out.items()}
 
     def reset(self, *, seed=None, options=None):
-        return obs_info_from_outputs(self._host(self.ora.reset()))
+        """FootsiesVectorEnv.reset: ``seed`` and ``options["mask"]`` / ``options["hard"]`` reach the oracle."""
+        options = options or {}
+        mask = options.get("mask")
+        out = self.ora.reset(seeds=reset_seeds(seed, self.num_envs),
+                             mask=None if mask is None else np.asarray(mask, dtype=np.uint8).reshape(self.num_envs),
+                             flags=_abi.FS_RESET_HARD if options.get("hard", False) else _abi.FS_RESET_IF_NEEDED)
+        return obs_info_from_outputs(self._host(out))
 
     def step(self, actions):
         out = self._host(self.ora.step(encode_actions(np.asarray(actions))))
