@@ -45,6 +45,7 @@ FS_KERNEL_POLICY = 2
 FS_KERNEL_PACKED = 4
 FS_KERNEL_SKIP_POLICY = 16
 FS_KERNEL_SELFPLAY = 32
+FS_KERNEL_SKIP_SELFPLAY = 64
 FS_SELFPLAY_MIRROR = 1
 FS_SKIP_POLICY_MAX_TICKS = 4096
 FS_PACKED_LANE_BYTES = 16
@@ -188,6 +189,8 @@ LIB_FUNCTIONS = {
                                       C.POINTER(fs_skip_traj)]),
     "fs_step_n_selfplay": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(fs_policy), C.POINTER(fs_policy), C.c_int,
                                      C.POINTER(fs_outputs)]),
+    "fs_step_skip_selfplay": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(fs_policy), C.POINTER(fs_policy), C.c_int,
+                                        C.c_int, C.POINTER(fs_outputs), C.POINTER(fs_skip_traj)]),
     "fs_ppo_workspace_bytes": (C.c_size_t, []),
     "fs_ppo_eval": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.POINTER(fs_mlp), C.POINTER(fs_mlp),
                               C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -698,6 +698,38 @@ FS_API int fs_step_n_policy(fs_handle h, int n, const fs_policy* pol, const uint
   return step_chunked(h, n, nullptr, p2_act, 0, traj, pol);
 }
 
+// The trajectory argument of the fused actor calls (fs_step_skip_policy, fs_step_n_selfplay,
+// fs_step_skip_selfplay): the handle's regular outputs when NULL, else the caller's buffers, every tick
+// output required and final_* in same-step auto-reset (`call` names the entry point in the message).
+static int traj_outputs(fs_handle h, const fs_outputs* traj, const char* call, fsk::DevOutputs& out) {
+  out = h->out;
+  if (!traj) return FS_OK;
+  out = fsk::DevOutputs{traj->guard,          traj->move,           traj->move_frame,  traj->position,
+                        traj->reward,         traj->terminated,     traj->truncated,   traj->frame,
+                        traj->action,         traj->hitstun,        traj->final_guard, traj->final_move,
+                        traj->final_move_frame, traj->final_position, traj->final_frame, traj->final_action,
+                        traj->final_hitstun};
+  const void* req[] = {traj->guard, traj->move,   traj->move_frame, traj->position, traj->reward,
+                       traj->terminated, traj->truncated, traj->frame, traj->action, traj->hitstun};
+  for (const void* q : req)
+    if (!q) return set_err(h, FS_E_INVALID, "%s: trajectory buffer missing", call);
+  if (h->cfg.autoreset_mode == FS_AUTORESET_SAME_STEP &&
+      (!traj->final_guard || !traj->final_move || !traj->final_move_frame || !traj->final_position ||
+       !traj->final_frame || !traj->final_action || !traj->final_hitstun))
+    return set_err(h, FS_E_INVALID, "%s: final_* trajectory buffers required in same-step autoreset", call);
+  return FS_OK;
+}
+
+// ... moved on by `row` trajectory rows: the first row of one launch of a call split by the row limit
+static void advance_rows(fsk::DevOutputs& o, uint64_t row) {
+  auto adv = [&](auto*& p, uint64_t per_row) { if (p) p += row * per_row; };
+  adv(o.guard, 2); adv(o.move, 2); adv(o.move_frame, 2); adv(o.position, 2);
+  adv(o.reward, 1); adv(o.terminated, 1); adv(o.truncated, 1); adv(o.frame, 1);
+  adv(o.action, 2); adv(o.hitstun, 2); adv(o.final_guard, 2); adv(o.final_move, 2);
+  adv(o.final_move_frame, 2); adv(o.final_position, 2); adv(o.final_frame, 1);
+  adv(o.final_action, 2); adv(o.final_hitstun, 2);
+}
+
 // the handles fs_step_skip / fs_step_skip_policy refuse (the message names the call)
 static const char* skip_unsupported(const fs_context* h) {
   if (h->cfg.p2_mode == FS_P2_EXTERNAL)  // (also with every arena switched to the bot: the handle's kind decides)
@@ -718,22 +750,8 @@ FS_API int fs_step_skip_policy(fs_handle h, int n, const fs_policy* pol, int max
   if (max_ticks < 1 || max_ticks > FS_SKIP_POLICY_MAX_TICKS)
     return set_err(h, FS_E_INVALID, "fs_step_skip_policy: max_ticks must be 1 .. %d (got %d)", FS_SKIP_POLICY_MAX_TICKS,
                    max_ticks);
-  fsk::DevOutputs out = h->out;
-  if (traj) {
-    out = fsk::DevOutputs{traj->guard,          traj->move,           traj->move_frame,  traj->position,
-                          traj->reward,         traj->terminated,     traj->truncated,   traj->frame,
-                          traj->action,         traj->hitstun,        traj->final_guard, traj->final_move,
-                          traj->final_move_frame, traj->final_position, traj->final_frame, traj->final_action,
-                          traj->final_hitstun};
-    const void* req[] = {traj->guard, traj->move,   traj->move_frame, traj->position, traj->reward,
-                         traj->terminated, traj->truncated, traj->frame, traj->action, traj->hitstun};
-    for (const void* q : req)
-      if (!q) return set_err(h, FS_E_INVALID, "fs_step_skip_policy: trajectory buffer missing");
-    if (h->cfg.autoreset_mode == FS_AUTORESET_SAME_STEP &&
-        (!traj->final_guard || !traj->final_move || !traj->final_move_frame || !traj->final_position ||
-         !traj->final_frame || !traj->final_action || !traj->final_hitstun))
-      return set_err(h, FS_E_INVALID, "fs_step_skip_policy: final_* trajectory buffers required in same-step autoreset");
-  }
+  fsk::DevOutputs out;
+  if (int rc = traj_outputs(h, traj, "fs_step_skip_policy", out)) return rc;
   int rc;
   if ((rc = use_device(h))) return rc;
   const uint64_t N = (uint64_t)h->n;
@@ -751,12 +769,7 @@ FS_API int fs_step_skip_policy(fs_handle h, int n, const fs_policy* pol, int max
     fsk::StepParams& sp = q.p;
     sp.st = h->st;
     sp.out = out;
-    auto adv = [&](auto*& p, uint64_t per_row) { if (p) p += row * per_row; };
-    adv(sp.out.guard, 2); adv(sp.out.move, 2); adv(sp.out.move_frame, 2); adv(sp.out.position, 2);
-    adv(sp.out.reward, 1); adv(sp.out.terminated, 1); adv(sp.out.truncated, 1); adv(sp.out.frame, 1);
-    adv(sp.out.action, 2); adv(sp.out.hitstun, 2); adv(sp.out.final_guard, 2); adv(sp.out.final_move, 2);
-    adv(sp.out.final_move_frame, 2); adv(sp.out.final_position, 2); adv(sp.out.final_frame, 1);
-    adv(sp.out.final_action, 2); adv(sp.out.final_hitstun, 2);
+    advance_rows(sp.out, row);
     sp.pol = fsk::PolicyParams{pol->w1, pol->b1, pol->w2, pol->b2, pol->w3, pol->b3,
                                pol->actions_out ? pol->actions_out + row_d : nullptr,
                                pol->logp_out ? pol->logp_out + row_d : nullptr, pol->seed};
@@ -800,22 +813,8 @@ FS_API int fs_step_n_selfplay(fs_handle h, int n, const fs_policy* p1, const fs_
   if (n <= 0) return set_err(h, FS_E_INVALID, "fs_step_n_selfplay: n must be > 0");
   if (flags & ~FS_SELFPLAY_MIRROR) return set_err(h, FS_E_INVALID, "fs_step_n_selfplay: bad flags %d", flags);
   if (const char* why = selfplay_unsupported(h)) return set_err(h, FS_E_UNSUPPORTED, "fs_step_n_selfplay: %s", why);
-  fsk::DevOutputs out = h->out;
-  if (traj) {
-    out = fsk::DevOutputs{traj->guard,          traj->move,           traj->move_frame,  traj->position,
-                          traj->reward,         traj->terminated,     traj->truncated,   traj->frame,
-                          traj->action,         traj->hitstun,        traj->final_guard, traj->final_move,
-                          traj->final_move_frame, traj->final_position, traj->final_frame, traj->final_action,
-                          traj->final_hitstun};
-    const void* req[] = {traj->guard, traj->move,   traj->move_frame, traj->position, traj->reward,
-                         traj->terminated, traj->truncated, traj->frame, traj->action, traj->hitstun};
-    for (const void* q : req)
-      if (!q) return set_err(h, FS_E_INVALID, "fs_step_n_selfplay: trajectory buffer missing");
-    if (h->cfg.autoreset_mode == FS_AUTORESET_SAME_STEP &&
-        (!traj->final_guard || !traj->final_move || !traj->final_move_frame || !traj->final_position ||
-         !traj->final_frame || !traj->final_action || !traj->final_hitstun))
-      return set_err(h, FS_E_INVALID, "fs_step_n_selfplay: final_* trajectory buffers required in same-step autoreset");
-  }
+  fsk::DevOutputs out;
+  if (int rc = traj_outputs(h, traj, "fs_step_n_selfplay", out)) return rc;
   int rc;
   if ((rc = use_device(h))) return rc;
   const uint64_t N = (uint64_t)h->n;
@@ -833,12 +832,7 @@ FS_API int fs_step_n_selfplay(fs_handle h, int n, const fs_policy* p1, const fs_
     fsk::StepParams& sp = q.p;
     sp.st = h->st;
     sp.out = out;
-    auto adv = [&](auto*& p, uint64_t per_row) { if (p) p += row * per_row; };
-    adv(sp.out.guard, 2); adv(sp.out.move, 2); adv(sp.out.move_frame, 2); adv(sp.out.position, 2);
-    adv(sp.out.reward, 1); adv(sp.out.terminated, 1); adv(sp.out.truncated, 1); adv(sp.out.frame, 1);
-    adv(sp.out.action, 2); adv(sp.out.hitstun, 2); adv(sp.out.final_guard, 2); adv(sp.out.final_move, 2);
-    adv(sp.out.final_move_frame, 2); adv(sp.out.final_position, 2); adv(sp.out.final_frame, 1);
-    adv(sp.out.final_action, 2); adv(sp.out.final_hitstun, 2);
+    advance_rows(sp.out, row);
     auto actor = [&](const fs_policy* pol) {
       return fsk::PolicyParams{pol->w1, pol->b1, pol->w2, pol->b2, pol->w3, pol->b3,
                                pol->actions_out ? pol->actions_out + row_s : nullptr,
@@ -856,6 +850,71 @@ FS_API int fs_step_n_selfplay(fs_handle h, int n, const fs_policy* p1, const fs_
     sp.arena_base = h->cfg.arena_base;
     sp.geom = h->geom;
     HIP_TRY(h, fsk::launch_step_selfplay(q, h->cfg.float_mode, h->stream));
+    h->steps += (uint64_t)m;
+    j += m;
+  }
+  return FS_OK;
+}
+
+FS_API int fs_step_skip_selfplay(fs_handle h, int n, const fs_policy* p1, const fs_policy* p2, int flags,
+                                 int max_ticks, const fs_outputs* traj, const fs_skip_traj* skip) {
+  if (!h) return FS_E_INVALID;
+  for (const fs_policy* pol : {p1, p2})
+    if (!pol || !pol->w1 || !pol->b1 || !pol->w2 || !pol->b2 || !pol->w3 || !pol->b3)
+      return set_err(h, FS_E_INVALID, "fs_step_skip_selfplay: all six weight arrays of both actors required");
+  if (n < 1) return set_err(h, FS_E_INVALID, "fs_step_skip_selfplay: n must be >= 1 (got %d)", n);
+  if (max_ticks < 1 || max_ticks > FS_SKIP_POLICY_MAX_TICKS)
+    return set_err(h, FS_E_INVALID, "fs_step_skip_selfplay: max_ticks must be 1 .. %d (got %d)",
+                   FS_SKIP_POLICY_MAX_TICKS, max_ticks);
+  if (flags & ~FS_SELFPLAY_MIRROR) return set_err(h, FS_E_INVALID, "fs_step_skip_selfplay: bad flags %d", flags);
+  // P2's draw counter is (decision index) + (tick in decision << 40): injective below 2^40 decisions
+  if (h->steps + (uint64_t)n >= (1ull << 40))
+    return set_err(h, FS_E_INVALID, "fs_step_skip_selfplay: fs_steps_taken + n must stay below 2^40");
+  if (const char* why = selfplay_unsupported(h)) return set_err(h, FS_E_UNSUPPORTED, "fs_step_skip_selfplay: %s", why);
+  const uint64_t N = (uint64_t)h->n;
+  if ((p2->actions_out || p2->logp_out) && (uint64_t)n * (uint64_t)max_ticks * N > 0x7fffffffull)
+    return set_err(h, FS_E_INVALID, "fs_step_skip_selfplay: n * max_ticks * N = %llu entries of P2's sample arrays "
+                                    "exceed int32", (unsigned long long)((uint64_t)n * (uint64_t)max_ticks * N));
+  fsk::DevOutputs out;
+  if (int rc = traj_outputs(h, traj, "fs_step_skip_selfplay", out)) return rc;
+  int rc;
+  if ((rc = use_device(h))) return rc;
+  uint64_t rows = kMaxLaunchRows;
+  if (const char* e = getenv("FOOTSIES_MAX_LAUNCH_ROWS"))  // (step_chunked's test hook)
+    rows = std::min<uint64_t>(rows, std::max<uint64_t>(1, strtoull(e, nullptr, 10)));
+  const int max_n = (int)std::max<uint64_t>(1, std::min<uint64_t>(rows / N, 0x7fffffff));
+  // fs_step_skip_policy's split: every launch ends on decision boundaries and both sampling
+  // streams are keyed by the decision counter (and the tick within the decision)
+  for (int j = 0; j < n;) {
+    const int m = std::min(max_n, n - j);
+    const uint64_t row = traj ? (uint64_t)j * N : 0;           // first output row of this launch
+    const uint64_t row_d = (uint64_t)j * N;                    // ... of the per-decision arrays
+    const uint64_t row_t = row_d * (uint64_t)max_ticks;        // ... of P2's per-tick arrays
+    fsk::SkipSelfPlayParams q{};
+    fsk::StepParams& sp = q.p;
+    sp.st = h->st;
+    sp.out = out;
+    advance_rows(sp.out, row);
+    auto actor = [&](const fs_policy* pol, uint64_t at) {
+      return fsk::PolicyParams{pol->w1, pol->b1, pol->w2, pol->b2, pol->w3, pol->b3,
+                               pol->actions_out ? pol->actions_out + at : nullptr,
+                               pol->logp_out ? pol->logp_out + at : nullptr, pol->seed};
+    };
+    sp.pol = actor(p1, row_d);
+    q.pol2 = actor(p2, row_t);
+    q.mirror = (flags & FS_SELFPLAY_MIRROR) != 0;
+    sp.n_envs = h->n;
+    sp.n_steps = m;
+    sp.out_stride_steps = traj ? 1 : 0;
+    sp.dense_reward = h->cfg.dense_reward;
+    sp.autoreset_mode = h->cfg.autoreset_mode;
+    sp.t0 = h->steps;
+    sp.arena_base = h->cfg.arena_base;
+    sp.geom = h->geom;
+    q.ticks_out = skip && skip->ticks ? skip->ticks + row_d : nullptr;
+    q.capped_out = skip && skip->capped ? skip->capped + row_d : nullptr;
+    q.max_ticks = max_ticks;
+    HIP_TRY(h, fsk::launch_step_skip_selfplay(q, h->cfg.float_mode, h->stream));
     h->steps += (uint64_t)m;
     j += m;
   }
@@ -1197,6 +1256,8 @@ FS_API const char* fs_step_kernel(fs_handle h, int n_steps, int flags) {
     return skip_unsupported(h) ? nullptr : fsk::step_skip_policy_kernel_name(h->cfg.float_mode, h->cfg.p2_mode);
   if (h && n_steps > 0 && flags == FS_KERNEL_SELFPLAY)
     return selfplay_unsupported(h) ? nullptr : fsk::step_selfplay_kernel_name(h->cfg.float_mode);
+  if (h && n_steps > 0 && flags == FS_KERNEL_SKIP_SELFPLAY)
+    return selfplay_unsupported(h) ? nullptr : fsk::step_skip_selfplay_kernel_name(h->cfg.float_mode);
   if (!h || n_steps <= 0 || (flags & ~(FS_KERNEL_HASHED | FS_KERNEL_POLICY | FS_KERNEL_PACKED))) return nullptr;
   return fsk::step_kernel_name((flags & FS_KERNEL_POLICY) != 0, (flags & FS_KERNEL_HASHED) != 0, n_steps, h->n,
                                h->cfg.float_mode, variant(h), h->geom, (flags & FS_KERNEL_PACKED) != 0,

@@ -129,6 +129,16 @@ struct SelfPlayParams {
   int mirror;         // FS_SELFPLAY_MIRROR: P2 sees the game from its own side, Left / Right exchanged
 };
 
+// fs_step_skip_selfplay (k_step_skip_selfplay): p.n_steps agent decisions per arena, P2's actor on every tick
+struct SkipSelfPlayParams {
+  StepParams p;         // p.pol: P1's actor, its outputs [n][N] by decision; p.t0: the first decision's index
+  PolicyParams pol2;    // P2's actor; its outputs [n][max_ticks][N] by (decision, tick) or null
+  int32_t* ticks_out;   // [n][N] or null
+  uint8_t* capped_out;  // [n][N] or null
+  int max_ticks;        // >= 1: closes a decision
+  int mirror;           // FS_SELFPLAY_MIRROR
+};
+
 struct ResetParams {
   DevState st;
   DevOutputs out;
@@ -171,6 +181,8 @@ const char* step_skip_policy_kernel_name(int float_mode, int p2_mode);
 // (FS_P2_EXTERNAL handles with no arena switched to the bot; fs_step_n_selfplay refuses the others)
 hipError_t launch_step_selfplay(const SelfPlayParams& q, int float_mode, hipStream_t s);
 const char* step_selfplay_kernel_name(int float_mode);
+hipError_t launch_step_skip_selfplay(const SkipSelfPlayParams& q, int float_mode, hipStream_t s);
+const char* step_skip_selfplay_kernel_name(int float_mode);
 hipError_t launch_reset(const ResetParams& p, int float_mode, hipStream_t s);
 hipError_t launch_set_p2(const DevState& st, int bot, const uint8_t* mask, int n, hipStream_t s);
 hipError_t launch_hash_actions(int n_envs, int n_steps, uint64_t seed, uint64_t t0, uint64_t arena_base, uint8_t* p1,

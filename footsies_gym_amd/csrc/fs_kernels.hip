@@ -2651,6 +2651,123 @@ __global__ __launch_bounds__(256) void k_step_n_selfplay(SelfPlayParams q) {
 }
 }  // namespace selfplay
 
+// fs_step_skip_selfplay: p.n_steps agent decisions per arena with the second actor playing P2 on
+// every tick, the ticks P1 skips included (the reference calls `opponent` inside every env.step,
+// FE:525-527, under wrappers/frame_skip.py:65-80).  P2's actor needs the converged wave on every
+// tick, so k_step_skip_policy's divergent pair loop cannot hold it: the loop here is over wave
+// ticks, and every pair carries its own decision index d, tick-in-decision j, f64 reward sum and
+// "at a decision boundary" flag.  Each wave tick both actors run for the whole wave (P1's only when
+// some arena of the wave is at a boundary: ahead in every A/B process); P1's sample is
+// taken by the arenas at a boundary only (the others' P1 input is 0); each arena with d < n runs
+// one env_step into output row d of its own, and closes its decision on k_step_skip's test or at
+// max_ticks.  The wave leaves when none of its arenas has a decision left, i.e. after its slowest
+// arena's sum of ticks over the n decisions, not the sum of the per-decision maxima
+// k_step_skip_policy pays.  Finished arenas and the lanes past the last arena stay in for the
+// actors and tick nothing; a wholly idle wave leaves.
+// Draws (policy_act_arena): P1's on counter t0 + d, fs_step_skip_policy's; P2's on (t0 + d) +
+// (j << 40), so with max_ticks = 1 both are fs_step_n_selfplay's and nothing depends on how a call
+// is split or which arenas share a wave.  P2's optional sample arrays are [n][max_ticks][N].
+// Both actors' fragments are read from their LDS images every wave tick: the per-arena counters
+// and the reward sum take the registers a resident set would (two waves per SIMD: 256 VGPRs).
+template <class C>
+__device__ __forceinline__ void skip_selfplay_body(const SkipSelfPlayParams& q) {
+  constexpr int P2 = C::P2;
+  static_assert(C::TP == kTabLds && P2 == FS_P2_EXTERNAL, "fs_step_skip_selfplay: a remote P2, played by the second actor");
+  const StepParams& p = q.p;
+  const int l = blockIdx.x * kBlock + threadIdx.x;
+  const bool active = l < 2 * p.n_envs;
+  const int a = active ? l >> 1 : 0;
+  const uint32_t k = l & 1;
+  Lane L;
+  load_lane<P2>(L, p.st, a, k);
+  if constexpr (C::GEOM) L.f.y = reinterpret_cast<const float*>(p.st.posy)[2 * a + (int)k];
+  stage_policy(p.pol);
+  stage_policy<true>(q.pol2, sPol2);
+  stage_tables<false>();
+  if ((l & ~63) >= 2 * p.n_envs) return;  // the whole wave is past the last arena
+  L.te = next_tick_entry<false>(L.f);
+  const uint32_t row_step = (uint32_t)p.out_stride_steps * (uint32_t)p.n_envs;
+  const uint32_t arena0 = (uint32_t)(l & ~63) >> 1;
+  const uint32_t mir = q.mirror ? 1u : 0u;
+  const uint32_t max_ticks = (uint32_t)q.max_ticks;
+  const uintptr_t slot = reinterpret_cast<uintptr_t>(&sSkipReward[threadIdx.x]);
+  const PolicyWeightsLds W1 = policy_weights_lds(sPol);
+  const PolicyWeightsLds W2 = policy_weights_lds(sPol2);
+  StepParams ps = p;
+  uint32_t none = 0;
+  const uint32_t n = active ? (uint32_t)p.n_steps : 0u;  // (a lane past the last arena has no decision to run)
+  uint32_t d = 0, j = 0;
+  double acc = 0.0;
+  bool boundary = true;
+  uint32_t a1 = 0;  // P1's sample of the decision under way
+  float lp1 = 0.0f;
+  uint32_t d0, d1;
+  policy_features(L, d0, d1);
+  while (__builtin_amdgcn_ballot_w64(d < n) != 0) {
+    const uint64_t t1 = p.t0 + (uint64_t)d;
+    const PolicyOut po2 = policy_act_arena(W2.fresh(), d0, d1, q.pol2.seed, p.arena_base + arena0,
+                                           t1 + ((uint64_t)j << 40), mir);
+    // P1's forward pass only when some arena of the wave starts a decision on this tick (wave-uniform)
+    PolicyOut po1{0u, 0.0f};
+    if (__builtin_amdgcn_ballot_w64(boundary && d < n) != 0)
+      po1 = policy_act_arena(W1.fresh(), d0, d1, p.pol.seed, p.arena_base + arena0, t1, 0u);
+    if (boundary) {
+      a1 = po1.action;
+      lp1 = po1.logp;
+    }
+    if (d < n) {
+      const uint32_t r = d * row_step + (uint32_t)a;  // the decision's output row
+      // the ticks' reward row: element r is this lane's slot of LDS (skip_body)
+      uintptr_t row = slot - 8ull * r;
+      asm volatile("" : "+v"(row));
+      ps.out.reward = reinterpret_cast<double*>(row);
+      uint32_t in = boundary ? a1 : 0u;
+      if (k) {
+        const uint32_t s = (d * max_ticks + j) * (uint32_t)p.n_envs + (uint32_t)a;
+        if (q.pol2.actions) q.pol2.actions[s] = (uint8_t)po2.action;
+        if (q.pol2.logp) q.pol2.logp[s] = po2.logp;
+        // P2's game input: Left (1) and Right (2) exchanged when it plays from its own side
+        const uint32_t flipped = (po2.action & 4u) | ((po2.action & 1u) << 1) | ((po2.action >> 1) & 1u);
+        in = mir ? flipped : po2.action;
+      }
+      env_step<FS_TICK(C)>(L, in, ps, r, none);
+      acc += ps.out.reward[r];
+      j++;
+      boundary = false;
+      const bool more = is_skippable(L) && !L.pending;
+      if (!more || j == max_ticks) {
+        if (k == 0) {
+          const uint32_t row_d = d * (uint32_t)p.n_envs + (uint32_t)a;
+          p.out.reward[r] = acc;
+          if (p.pol.actions) p.pol.actions[row_d] = (uint8_t)a1;
+          if (p.pol.logp) p.pol.logp[row_d] = lp1;
+          if (q.ticks_out) q.ticks_out[row_d] = (int32_t)j;
+          if (q.capped_out) q.capped_out[row_d] = more ? 1 : 0;
+        }
+        d++;
+        j = 0;
+        acc = 0.0;
+        boundary = true;
+      }
+    }
+    policy_features(L, d0, d1);
+  }
+  if (active) {
+    store_lane<P2>(L, p.st, a);
+    if constexpr (C::GEOM) reinterpret_cast<float*>(p.st.posy)[2 * a + (int)k] = L.f.y;
+  }
+}
+
+// (the general-geometry tick behind a launch-uniform branch, as in k_step_n; in the selfplay namespace
+// like its neighbour above)
+namespace selfplay {
+template <int FM>
+__global__ __launch_bounds__(256) void k_step_skip_selfplay(SkipSelfPlayParams q) {
+  if (q.p.geom) skip_selfplay_body<TickCfg<FM, FS_P2_EXTERNAL, kPolicy, kGeom>>(q);
+  else skip_selfplay_body<TickCfg<FM, FS_P2_EXTERNAL, kPolicy>>(q);
+}
+}  // namespace selfplay
+
 // FootsiesEnv.reset (FE:482-515) / RESET (BC:143-146) / game start (BC:105-128), every handle
 // kind through the per-arena actor logic (off the throughput path).
 template <int FM>
@@ -3112,6 +3229,20 @@ hipError_t launch_step_selfplay(const SelfPlayParams& q_in, int float_mode, hipS
 const char* step_selfplay_kernel_name(int float_mode) {
   static thread_local char buf[64];
   snprintf(buf, sizeof buf, "fsk::selfplay::k_step_n_selfplay<%d>", float_mode == FS_FLOAT_DOUBLE);
+  return buf;
+}
+
+// (named after every other kernel)
+hipError_t launch_step_skip_selfplay(const SkipSelfPlayParams& q, int float_mode, hipStream_t s) {
+  const dim3 grid = grid_for(2 * q.p.n_envs), block(kBlock);
+  if (float_mode == FS_FLOAT_DOUBLE) hipLaunchKernelGGL(selfplay::k_step_skip_selfplay<FS_FLOAT_DOUBLE>, grid, block, 0, s, q);
+  else hipLaunchKernelGGL(selfplay::k_step_skip_selfplay<FS_FLOAT_STRICT32>, grid, block, 0, s, q);
+  return hipGetLastError();
+}
+
+const char* step_skip_selfplay_kernel_name(int float_mode) {
+  static thread_local char buf[64];
+  snprintf(buf, sizeof buf, "fsk::selfplay::k_step_skip_selfplay<%d>", float_mode == FS_FLOAT_DOUBLE);
   return buf;
 }
 

@@ -26,7 +26,7 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 constexpr int kPolFrags = 17;  // a1[2] | a2[u=2][t,s=4] | a2b[2] | a3[4] | a3b
 constexpr int kPolA1 = 0, kPolA2 = 2, kPolA2b = 10, kPolA3 = 12, kPolA3b = 16;
 __shared__ bf16x8 sPol[kPolFrags][64];  // every wave of the block reads the same image
-__shared__ bf16x8 sPol2[kPolFrags][64];  // k_step_n_selfplay: P2's actor, read every tick (PolicyWeightsLds)
+__shared__ bf16x8 sPol2[kPolFrags][64];  // the self-play kernels: P2's actor, read every tick (PolicyWeightsLds)
 
 __device__ __forceinline__ f32x16 mfma(bf16x8 a, bf16x8 b, f32x16 c) {
   return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
@@ -174,7 +174,10 @@ __device__ __forceinline__ PolicyWeightsLds policy_weights_lds(bf16x8 (&img)[kPo
 // (FS_SELFPLAY_MIRROR, wave-uniform): the game from P2's side -- each feature pair swapped (the
 // gather takes pair lane 2r + 1 first) and both positions negated (the sign bits of the two bf16
 // positions); the arithmetic is the same.
-template <class WS>
+// ARENA_T (k_step_skip_selfplay, whose arenas are each at a decision and tick of their own): `t` is
+// the draw counter of this pair lane's arena, the same on both lanes of the pair; MFMA lane r takes
+// arena r's from pair lane 2r as it takes the features.  Otherwise `t` is wave-uniform.
+template <class WS, bool ARENA_T = false>
 __device__ __forceinline__ PolicyOut policy_act_side(const WS& W, uint32_t d0, uint32_t d1, uint64_t seed,
                                                      uint64_t arena0, uint64_t t, uint32_t mir) {
   const int l = threadIdx.x & 63, r = l & 31, h = l >> 5;
@@ -227,7 +230,10 @@ __device__ __forceinline__ PolicyOut policy_act_side(const WS& W, uint32_t d0, u
   const float s_other = lane_read(s_mine, l ^ 32);
   const float s_lo = h == 0 ? s_mine : s_other, s_hi = h == 0 ? s_other : s_mine;
   const float total = s_lo + s_hi;
-  const float target = policy_uniform(seed, arena0 + (uint64_t)r, t) * total;
+  uint64_t tr = t;
+  if constexpr (ARENA_T)
+    tr = (uint64_t)lane_read((uint32_t)t, 2 * r) | ((uint64_t)lane_read((uint32_t)(t >> 32), 2 * r) << 32);
+  const float target = policy_uniform(seed, arena0 + (uint64_t)r, tr) * total;
   // first action whose cumulative weight exceeds the target (half h = 0 starts at 0, h = 1 at s_lo)
   const float base = h == 0 ? 0.0f : s_lo;
   const float c0 = base + e0, c1 = c0 + e1, c2 = c1 + e2;
@@ -250,6 +256,13 @@ __device__ __forceinline__ PolicyOut policy_act_side(const WS& W, uint32_t d0, u
 __device__ __forceinline__ PolicyOut policy_act(const PolicyWeights& W, uint32_t d0, uint32_t d1, uint64_t seed,
                                                 uint64_t arena0, uint64_t t) {
   return policy_act_side(W, d0, d1, seed, arena0, t, 0u);
+}
+
+// policy_act_side with a draw counter per arena (ARENA_T above)
+template <class WS>
+__device__ __forceinline__ PolicyOut policy_act_arena(const WS& W, uint32_t d0, uint32_t d1, uint64_t seed,
+                                                      uint64_t arena0, uint64_t t_arena, uint32_t mir) {
+  return policy_act_side<WS, true>(W, d0, d1, seed, arena0, t_arena, mir);
 }
 
 }  // namespace fsk

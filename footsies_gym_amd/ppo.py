@@ -349,6 +349,13 @@ class PPOTrainer:
     and `stats["opponent_age"]` holds the updates since.  P2's samples are not learnt from.
     Data-parallel ranks hold identical weights and refresh at the same update.
 
+    `self_play="decisions"` is both at once, the reference's FootsiesFrameSkipped over an env with a
+    custom `opponent`: `horizon` counts P1's decisions as under `frame_skip=True` (capped by
+    `max_skip_ticks`) while the frozen mirrored copy plays P2 on every tick, the skipped ones included,
+    in one fs_step_skip_selfplay launch per rollout (FusedSelfPlayRollout.rollout_skipped).  `stats`
+    holds the frame-skip and the self-play entries.  `frame_skip` is implied; `self_play=True` stays
+    per tick and still refuses `frame_skip=True`.
+
     Data-parallel (`group`: a torch.distributed process group, or "default" for the default one;
     SURVEY.md §8(e)): one trainer per rank, each over its own FootsiesSim (a ShardedSim's handle:
     its arena_base keys the actor's sampling stream, so ranks roll out different arenas), all with
@@ -364,11 +371,16 @@ class PPOTrainer:
                  kl_ticks=None, learner_precision="split_bf16", group=None, frame_skip=False, max_skip_ticks=64,
                  self_play=False, opponent_refresh=1, opponent_seed=None):
         torch = _torch()
+        decisions = isinstance(self_play, str)
+        if decisions and self_play != "decisions":
+            raise ValueError("self_play must be False, True (per tick) or 'decisions', got %r" % (self_play,))
         if self_play and sim.p2_mode != "external":
             raise ValueError("self_play needs a sim created with p2_mode='external' (the second actor plays P2), "
                              "got %r" % (sim.p2_mode,))
-        if self_play and frame_skip:
-            raise ValueError("self_play with frame_skip=True is not built (fs_step_skip_policy has no second actor)")
+        if self_play and frame_skip and not decisions:
+            raise ValueError("self_play=True is per tick and takes no frame_skip=True: use self_play='decisions' "
+                             "(fs_step_skip_selfplay)")
+        frame_skip = frame_skip or decisions
         if self_play and int(opponent_refresh) < 1:
             raise ValueError("opponent_refresh must be >= 1, got %r" % (opponent_refresh,))
         if old_logp not in ("behaviour", "fp32"):
@@ -447,6 +459,7 @@ class PPOTrainer:
         torch = _torch()
         first = self._next_first if self._next_first is not None else obs_features(self.sim.outputs())
         if self.frame_skip:  # a row per agent decision: its last tick, the rewards of its ticks summed
+            # (self_play="decisions": the same call on FusedSelfPlayRollout, P2's samples not stored)
             self.rollout.rollout_skipped(self.horizon, self.actions, self.logp, self.ticks, self.capped,
                                          trajectory=self.traj, max_ticks=self.max_skip_ticks)
         elif self.self_play:  # P2's samples are not learnt from: not stored

@@ -16,7 +16,9 @@ policy-driven ticks is one kernel launch with the arena state in registers throu
 asked once per decision and each arena skipping its own frames as under FootsiesFrameSkipped.
 
 :class:`FusedSelfPlayRollout` adds a second in-kernel actor for P2 (fs_step_n_selfplay): self-play,
-or any learned opponent of the same shape, with both fighters reacting every tick inside one launch.
+or any learned opponent of the same shape, with both fighters reacting every tick inside one launch;
+its ``rollout_skipped`` (fs_step_skip_selfplay) runs agent decisions instead, P1's actor asked once per
+decision and the opponent on every tick, the ones P1 skips included.
 """
 import ctypes as C
 
@@ -280,6 +282,53 @@ class FusedSelfPlayRollout(FusedPolicyRollout):
                                        None if t is None else C.byref(t)), self.sim.handle)
         return tuple(out)
 
-    def rollout_skipped(self, *args, **kwargs):
-        raise NotImplementedError("self-play per agent decision is not built: P2 would have to act inside P1's "
-                                  "skipped frames (fs_step_skip_policy has no second actor)")
+    def rollout_skipped(self, n, actions=None, logp=None, ticks=None, capped=None, p2_actions=False, p2_logp=False,
+                        trajectory=None, max_ticks=_abi.FS_SKIP_DEFAULT_MAX_TICKS):
+        """n agent decisions per arena in one launch (fs_step_skip_selfplay): P1's actor is asked once
+        per decision and the arena skips the frames in which P1 cannot act, as in
+        FusedPolicyRollout.rollout_skipped, while the opponent acts on every tick, the skipped ones
+        included -- the reference's FootsiesFrameSkipped over an env with a custom `opponent`.
+        `actions` / `logp` / `ticks` / `capped` are [n][N] by decision (allocated when None, pass False
+        to skip one).  `p2_actions` (uint8) / `p2_logp` (float32) are [n][max_ticks][N] by decision and
+        tick within it -- the opponent's sampled index before swap_left_right -- and off by default:
+        pass None to have one allocated (entries of ticks that did not run are left as they were) or a
+        tensor of that shape.  Returns (actions, logp, ticks); `last_capped` holds the call's capped
+        flags and `last_p2` the (p2_actions, p2_logp) pair (False where off)."""
+        n, max_ticks = int(n), int(max_ticks)
+        if n < 1:
+            raise ValueError("rollout_skipped: n must be >= 1, got %d" % n)
+        if not 1 <= max_ticks <= _abi.FS_SKIP_POLICY_MAX_TICKS:
+            raise ValueError("rollout_skipped: max_ticks must be 1 .. %d, got %d" % (_abi.FS_SKIP_POLICY_MAX_TICKS, max_ticks))
+        torch = _torch()
+        N, dev = self.sim.num_envs, self.sim.device
+        if actions is None:
+            actions = torch.empty((n, N), dtype=torch.uint8, device=dev)
+        if logp is None:
+            logp = torch.empty((n, N), dtype=torch.float32, device=dev)
+        if ticks is None:
+            ticks = torch.empty((n, N), dtype=torch.int32, device=dev)
+        if capped is None:
+            capped = torch.empty((n, N), dtype=torch.uint8, device=dev)
+        if p2_actions is None:
+            p2_actions = torch.empty((n, max_ticks, N), dtype=torch.uint8, device=dev)
+        if p2_logp is None:
+            p2_logp = torch.empty((n, max_ticks, N), dtype=torch.float32, device=dev)
+
+        def actor(w, seed, a, lp):
+            return _abi.fs_policy(w1=w[0].data_ptr(), b1=w[1].data_ptr(), w2=w[2].data_ptr(), b2=w[3].data_ptr(),
+                                  w3=w[4].data_ptr(), b3=w[5].data_ptr(), seed=seed,
+                                  actions_out=a.data_ptr() if a is not False else None,
+                                  logp_out=lp.data_ptr() if lp is not False else None)
+        p1 = actor(self.params, self.seed, actions, logp)
+        p2 = actor(self.params2, self.opponent_seed, p2_actions, p2_logp)
+        skip = _abi.fs_skip_traj(ticks=ticks.data_ptr() if ticks is not False else None,
+                                 capped=capped.data_ptr() if capped is not False else None)
+        t = None
+        if trajectory is not None:
+            t = _abi.fs_outputs(**{k: trajectory[k].data_ptr() for k in _abi.OUTPUT_SPEC if k in trajectory})
+        check(lib().fs_step_skip_selfplay(self.sim.handle, n, C.byref(p1), C.byref(p2),
+                                          _abi.FS_SELFPLAY_MIRROR if self.mirror else 0, max_ticks,
+                                          None if t is None else C.byref(t), C.byref(skip)), self.sim.handle)
+        self.last_capped = capped
+        self.last_p2 = (p2_actions, p2_logp)
+        return actions, logp, ticks

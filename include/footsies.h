@@ -417,6 +417,34 @@ int fs_step_skip_policy(fs_handle h, int n, const fs_policy* pol, int max_ticks,
 int fs_step_n_selfplay(fs_handle h, int n, const fs_policy* p1, const fs_policy* p2, int flags,
                        const fs_outputs* traj);
 
+/* Self-play per agent decision in one launch: fs_step_skip_policy with fs_step_n_selfplay's second
+ * actor, i.e. the reference's FootsiesFrameSkipped over a FootsiesEnv with a custom `opponent`
+ * (wrappers/frame_skip.py:65-80 calls env.step once per tick, and FE:525-527 asks `opponent`
+ * inside every env.step).  P1's actor decides once per decision -- the tick that takes its action,
+ * then input 0 while the arena's observation is skippable and the episode goes on, exactly as in
+ * fs_step_skip_policy -- and P2's actor acts on every tick, the ticks P1 skips included, on the
+ * observation as it stands before that tick.  flags: 0 or FS_SELFPLAY_MIRROR, as in
+ * fs_step_n_selfplay.  Draws, for arena i's decision d (counter c = fs_steps_taken + d):
+ *   P1: u = uniform(p1->seed, cfg.arena_base + i, c), fs_step_skip_policy's;
+ *   P2 on tick j of the decision: u = uniform(p2->seed, cfg.arena_base + i, c + ((uint64_t)j << 40)),
+ * so results depend neither on how a call is split nor on the other arenas, and with max_ticks = 1
+ * the call is fs_step_n_selfplay bit for bit.
+ *   traj, skip->ticks, skip->capped, p1->actions_out, p1->logp_out: by decision, as in
+ *     fs_step_skip_policy (the row is the decision's last tick, `reward` the float64 sum of its
+ *     ticks' rewards in tick order from 0.0; a FS_AUTORESET_NEXT_STEP arena with a reset pending
+ *     runs the reset burst alone, ticks = 1, reward = 0, both samples recorded and ignored).
+ *   p2->actions_out / p2->logp_out: optional, device [n][max_ticks][N]: entry (d, j, i) is P2's
+ *     sampled index (before the Left/Right exchange) and its log-probability on tick j of arena i's
+ *     decision d; entries of ticks that did not run are left untouched.  For tests and diagnostics.
+ * fs_steps_taken advances by n.  Asynchronous on the handle's stream; n * N above the trajectory
+ * row limit runs as consecutive launches that end on decision boundaries (identical results).
+ * FS_E_UNSUPPORTED where fs_step_n_selfplay returns it; FS_E_INVALID for n < 1, max_ticks outside
+ * 1 .. FS_SKIP_POLICY_MAX_TICKS, unknown flag bits, a NULL actor or weight array, fs_steps_taken +
+ * n >= 2^40 (P2's counter would repeat), or n * max_ticks * N above INT32_MAX when a P2 array is
+ * given.  (ABI 8: an addition) */
+int fs_step_skip_selfplay(fs_handle h, int n, const fs_policy* p1, const fs_policy* p2, int flags,
+                          int max_ticks, const fs_outputs* traj, const fs_skip_traj* skip);
+
 /* The C5 learner (footsies_gym_amd/ppo.py, PPOTrainer(learner="hip")): an MLP
  * 8 -> 64 -> tanh -> 64 -> tanh -> out, fp32 device weights in torch nn.Linear layouts. */
 typedef struct fs_mlp {
@@ -604,6 +632,9 @@ uint64_t fs_steps_taken(fs_handle h);
 #define FS_KERNEL_SKIP_POLICY 16
 /* fs_step_n_selfplay (alone; "fsk::selfplay::k_step_n_selfplay<0>"): NULL on a handle the call refuses */
 #define FS_KERNEL_SELFPLAY 32
+/* fs_step_skip_selfplay (alone; n_steps = decisions; "fsk::selfplay::k_step_skip_selfplay<0>"): NULL on a
+ * handle the call refuses */
+#define FS_KERNEL_SKIP_SELFPLAY 64
 const char* fs_step_kernel(fs_handle h, int n_steps, int flags);
 void fs_destroy(fs_handle h);
 /* Last error message of h (or of the last failed fs_create when h is NULL). */
