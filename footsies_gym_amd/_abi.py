@@ -103,6 +103,14 @@ OUTPUT_SPEC = {
 }
 
 
+def trajectory_outputs(trajectory):
+    """The fs_outputs of a trajectory dict (the OUTPUT_SPEC fields it holds, as device tensors), or
+    None for None: the `traj` argument of the fused step calls."""
+    if trajectory is None:
+        return None
+    return fs_outputs(**{k: trajectory[k].data_ptr() for k in OUTPUT_SPEC if k in trajectory})
+
+
 class fs_host_arrays(C.Structure):
     _fields_ = [(name, C.c_void_p) for name in (
         "guard", "move", "move_frame", "position", "info_guard", "info_move", "info_move_frame", "info_position",

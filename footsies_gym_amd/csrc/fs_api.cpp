@@ -381,12 +381,18 @@ FS_API int fs_reset(fs_handle h, const uint64_t* seeds, const uint8_t* mask, int
   return FS_OK;
 }
 
-static int step_common(fs_handle h, int n, const uint8_t* p1, const uint8_t* p2, int flags, uint64_t seed,
-                       const fs_outputs* traj, const uint8_t* active = nullptr,
-                       const fs_policy* pol = nullptr, const fs_packed_traj* pk = nullptr, void* rec = nullptr) {
-  int rc;
-  if ((rc = use_device(h))) return rc;
-  const size_t N = (size_t)h->n;
+// -- what the step entry points share: one parameter builder, one launch split, one of each check ------
+
+namespace {
+
+// Every handle-derived field of a launch's fsk::StepParams, for `n` steps into the handle's own
+// outputs; the caller adds what is its own (actions, trajectory rows, actors, seed, records).
+// Invariant to keep: every launcher receives the same bytes as if its entry point had set only the
+// fields its kernels read.  The kernels of the skip calls do not read p1_bot, and those of the
+// self-play calls read none of p1_bot, p2_resets, p2_noop; these calls only accept handles on which
+// the fields are 0 anyway (the skip calls refuse FS_P1_BOT, the self-play calls require
+// FS_P2_EXTERNAL and refuse FS_P1_BOT).  A field added here reaches every call.
+fsk::StepParams step_params(const fs_context* h, int n) {
   fsk::StepParams sp{};
   sp.st = h->st;
   sp.out = h->out;
@@ -395,16 +401,79 @@ static int step_common(fs_handle h, int n, const uint8_t* p1, const uint8_t* p2,
   sp.out_stride_steps = 0;
   sp.dense_reward = h->cfg.dense_reward;
   sp.autoreset_mode = h->cfg.autoreset_mode;
-  sp.action_seed = seed;
   sp.t0 = h->steps;
   sp.arena_base = h->cfg.arena_base;
   sp.p1_bot = h->cfg.p1_mode == FS_P1_BOT;
   sp.p2_resets = h->cfg.p2_mode == FS_P2_BOT;
   sp.p2_noop = h->cfg.p2_mode == FS_P2_NOOP;
   sp.geom = h->geom;
-  sp.rec = static_cast<uint2*>(rec);  // (one-tick launches only: fs_step_rec)
-  if (pol) sp.pol = fsk::PolicyParams{pol->w1, pol->b1, pol->w2, pol->b2, pol->w3, pol->b3,
-                                      pol->actions_out, pol->logp_out, pol->seed};
+  return sp;
+}
+
+// A call's trajectory argument: the handle's regular outputs when NULL, else the caller's buffers,
+// every tick output required and final_* in same-step auto-reset (`call` names the entry point in
+// the message).
+int traj_outputs(fs_handle h, const fs_outputs* traj, const char* call, fsk::DevOutputs& out) {
+  out = h->out;
+  if (!traj) return FS_OK;
+  out = fsk::DevOutputs{traj->guard,          traj->move,           traj->move_frame,  traj->position,
+                        traj->reward,         traj->terminated,     traj->truncated,   traj->frame,
+                        traj->action,         traj->hitstun,        traj->final_guard, traj->final_move,
+                        traj->final_move_frame, traj->final_position, traj->final_frame, traj->final_action,
+                        traj->final_hitstun};
+  const void* req[] = {traj->guard, traj->move,   traj->move_frame, traj->position, traj->reward,
+                       traj->terminated, traj->truncated, traj->frame, traj->action, traj->hitstun};
+  for (const void* q : req)
+    if (!q) return set_err(h, FS_E_INVALID, "%s: trajectory buffer missing", call);
+  if (h->cfg.autoreset_mode == FS_AUTORESET_SAME_STEP &&
+      (!traj->final_guard || !traj->final_move || !traj->final_move_frame || !traj->final_position ||
+       !traj->final_frame || !traj->final_action || !traj->final_hitstun))
+    return set_err(h, FS_E_INVALID, "%s: final_* trajectory buffers required in same-step autoreset", call);
+  return FS_OK;
+}
+
+// ... moved on by `row` trajectory rows: the first row of one launch of a call split by the row limit
+void advance_rows(fsk::DevOutputs& o, uint64_t row) {
+  auto adv = [&](auto*& p, uint64_t per_row) { if (p) p += row * per_row; };
+  adv(o.guard, 2); adv(o.move, 2); adv(o.move_frame, 2); adv(o.position, 2);
+  adv(o.reward, 1); adv(o.terminated, 1); adv(o.truncated, 1); adv(o.frame, 1);
+  adv(o.action, 2); adv(o.hitstun, 2); adv(o.final_guard, 2); adv(o.final_move, 2);
+  adv(o.final_move_frame, 2); adv(o.final_position, 2); adv(o.final_frame, 1);
+  adv(o.final_action, 2); adv(o.final_hitstun, 2);
+  adv(o.pk_lanes, 2); adv(o.pk_final, 2);  // (a packed trajectory: two 16-B lane records per row)
+}
+
+// an actor argument with all six weight arrays
+bool has_weights(const fs_policy* pol) {
+  if (!pol || !pol->w1 || !pol->b1 || !pol->w2 || !pol->b2 || !pol->w3 || !pol->b3) return false;
+  return true;
+}
+
+// an in-kernel actor whose sample arrays start at entry `at`
+fsk::PolicyParams policy_params(const fs_policy* pol, uint64_t at) {
+  return fsk::PolicyParams{pol->w1, pol->b1, pol->w2, pol->b2, pol->w3, pol->b3,
+                           pol->actions_out ? pol->actions_out + at : nullptr,
+                           pol->logp_out ? pol->logp_out + at : nullptr, pol->seed};
+}
+
+// what a one-tick or fused-tick launch takes besides its actions
+struct StepExtras {
+  const fsk::DevOutputs* traj = nullptr;  // the rows this launch writes, checked by the caller; else the handle's outputs
+  const fsk::PolicyParams* pol = nullptr; // fs_step_n_policy: P1's in-kernel actor
+  const uint8_t* active = nullptr;        // fs_step_masked
+  void* rec = nullptr;                    // fs_step_rec
+};
+
+int step_common(fs_handle h, int n, const uint8_t* p1, const uint8_t* p2, int flags, uint64_t seed,
+                const StepExtras& x = {}) {
+  int rc;
+  if ((rc = use_device(h))) return rc;
+  const size_t N = (size_t)h->n;
+  fsk::StepParams sp = step_params(h, n);
+  sp.action_seed = seed;
+  sp.rec = static_cast<uint2*>(x.rec);  // (one-tick launches only: fs_step_rec)
+  if (x.pol) sp.pol = *x.pol;
+  const uint8_t* active = x.active;
   const bool ext = h->cfg.p2_mode == FS_P2_EXTERNAL;
   const bool p1_bot = h->cfg.p1_mode == FS_P1_BOT;
   if (flags == FS_ACT_HOST && (p1 || p1_bot) && !active && N <= (size_t)fsk::kInlineArenas) {
@@ -436,30 +505,12 @@ static int step_common(fs_handle h, int n, const uint8_t* p1, const uint8_t* p2,
   } else {
     // P1 bot with explicit P2 rows (or records to write, which only k_step does): P1's row is
     // never read, but a null p1 would select the hashed-action kernel, so it points at the staging row
-    sp.p1 = (p1_bot && !p1 && (p2 || rec)) ? h->d_act : p1;
+    sp.p1 = (p1_bot && !p1 && (p2 || x.rec)) ? h->d_act : p1;
     sp.p2 = ext ? p2 : nullptr;
     sp.active = active;
   }
-  if (traj) {
-    sp.out = fsk::DevOutputs{traj->guard,          traj->move,           traj->move_frame,  traj->position,
-                             traj->reward,         traj->terminated,     traj->truncated,   traj->frame,
-                             traj->action,         traj->hitstun,        traj->final_guard, traj->final_move,
-                             traj->final_move_frame, traj->final_position, traj->final_frame, traj->final_action,
-                             traj->final_hitstun};
-    const void* req[] = {traj->guard, traj->move,   traj->move_frame, traj->position, traj->reward,
-                         traj->terminated, traj->truncated, traj->frame, traj->action, traj->hitstun};
-    for (const void* q : req)
-      if (!q) return set_err(h, FS_E_INVALID, "fs_step_n: trajectory buffer missing");
-    if (h->cfg.autoreset_mode == FS_AUTORESET_SAME_STEP &&
-        (!traj->final_guard || !traj->final_move || !traj->final_move_frame || !traj->final_position ||
-         !traj->final_frame || !traj->final_action || !traj->final_hitstun))
-      return set_err(h, FS_E_INVALID, "fs_step_n: final_* trajectory buffers required in same-step autoreset");
-    sp.out_stride_steps = 1;
-  } else if (pk) {  // (fs_step_n_packed validated the buffers)
-    sp.out = fsk::DevOutputs{};
-    sp.out.reward = pk->reward;
-    sp.out.pk_lanes = static_cast<uint4*>(pk->lanes);
-    sp.out.pk_final = static_cast<uint4*>(pk->final_lanes);
+  if (x.traj) {
+    sp.out = *x.traj;
     sp.out_stride_steps = 1;
   } else if (n > 1 && h->cfg.frame_delay > 0) {
     // the delayed queue needs every step's row, which a fused launch without a
@@ -467,8 +518,7 @@ static int step_common(fs_handle h, int n, const uint8_t* p1, const uint8_t* p2,
     for (int j = 0; j < n; j++) {
       const uint8_t* q1 = sp.p1 ? sp.p1 + (size_t)j * N : nullptr;
       const uint8_t* q2 = sp.p2 ? sp.p2 + (size_t)j * N : nullptr;
-      if ((rc = step_common(h, 1, q1 ? q1 : (p1_bot ? h->d_act : nullptr), q2, FS_ACT_DEVICE, seed, nullptr)))
-        return rc;
+      if ((rc = step_common(h, 1, q1 ? q1 : (p1_bot ? h->d_act : nullptr), q2, FS_ACT_DEVICE, seed))) return rc;
     }
     return FS_OK;
   }
@@ -481,52 +531,111 @@ static int step_common(fs_handle h, int n, const uint8_t* p1, const uint8_t* p2,
 // The kernels address trajectory rows with 32-bit byte offsets (row t of arena a at
 // (t * N + a) * element size, up to 8 B for the f64 reward), so one launch covers at most
 // kMaxLaunchRows arena-ticks; longer fused calls run as consecutive launches over row ranges
-// of the same buffers.  Hashed actions and the actor's sampling stream are keyed by the
-// handle's step counter, which each launch advances, so the split is invisible in the results.
+// of the same buffers.  Hashed actions and the actors' sampling streams are keyed by the
+// handle's step counter, which each launch advances, so the split is invisible in the results
+// (the skip calls' launches end on decision boundaries).
 constexpr uint64_t kMaxLaunchRows = 0xFFFFFFFFull / 8u;
 // (a packed trajectory's lane records: 32 B per row)
 constexpr uint64_t kMaxPackedLaunchRows = 0xFFFFFFFFull / 32u;
 
-static int step_chunked(fs_handle h, int n, const uint8_t* p1, const uint8_t* p2, uint64_t seed,
-                        const fs_outputs* traj, const fs_policy* pol, const fs_packed_traj* pk = nullptr) {
-  const uint64_t N = (uint64_t)h->n;
-  uint64_t rows = pk ? kMaxPackedLaunchRows : kMaxLaunchRows;
+// the steps one launch of a fused call may cover, `rows` being its kind's limit
+int max_launch_steps(const fs_context* h, uint64_t rows) {
   if (const char* e = getenv("FOOTSIES_MAX_LAUNCH_ROWS"))  // test hook: exercise the split at small sizes
     rows = std::min<uint64_t>(rows, std::max<uint64_t>(1, strtoull(e, nullptr, 10)));
-  const int max_n = (int)std::max<uint64_t>(1, std::min<uint64_t>(rows / N, 0x7fffffff));
-  if (n <= max_n) return step_common(h, n, p1, p2, FS_ACT_DEVICE, seed, traj, nullptr, pol, pk);
+  return (int)std::max<uint64_t>(1, std::min<uint64_t>(rows / (uint64_t)h->n, 0x7fffffff));
+}
+
+// `n` steps as launches of at most `max_n`: launch(j, m) issues steps j .. j + m - 1 and advances
+// h->steps by m itself, so that the next launch's counters start where this one's end
+template <typename Launch>
+int split_launches(int n, int max_n, Launch&& launch) {
   for (int j = 0; j < n;) {
     const int m = std::min(max_n, n - j);
-    const uint64_t row = (uint64_t)j * N;  // first arena-tick row of this launch
-    fs_outputs t{};
-    if (traj) {
-      t = *traj;
-      auto adv = [&](auto*& q, uint64_t per_row) { if (q) q += row * per_row; };
-      adv(t.guard, 2); adv(t.move, 2); adv(t.move_frame, 2); adv(t.position, 2); adv(t.reward, 1);
-      adv(t.terminated, 1); adv(t.truncated, 1); adv(t.frame, 1); adv(t.action, 2); adv(t.hitstun, 2);
-      adv(t.final_guard, 2); adv(t.final_move, 2); adv(t.final_move_frame, 2); adv(t.final_position, 2);
-      adv(t.final_frame, 1); adv(t.final_action, 2); adv(t.final_hitstun, 2);
-    }
-    fs_policy q{};
-    if (pol) {
-      q = *pol;
-      if (q.actions_out) q.actions_out += row;
-      if (q.logp_out) q.logp_out += row;
-    }
-    fs_packed_traj k{};
-    if (pk) {
-      k = *pk;
-      k.lanes = static_cast<char*>(k.lanes) + row * 2 * FS_PACKED_LANE_BYTES;
-      k.reward += row;
-      if (k.final_lanes) k.final_lanes = static_cast<char*>(k.final_lanes) + row * 2 * FS_PACKED_LANE_BYTES;
-    }
-    const int rc = step_common(h, m, p1 ? p1 + row : nullptr, p2 ? p2 + row : nullptr, FS_ACT_DEVICE, seed,
-                               traj ? &t : nullptr, nullptr, pol ? &q : nullptr, pk ? &k : nullptr);
-    if (rc) return rc;
+    if (int rc = launch(j, m)) return rc;
     j += m;
   }
   return FS_OK;
 }
+
+// fs_step_n / fs_step_n_policy / fs_step_n_packed: step_common over row ranges of the caller's buffers
+int step_chunked(fs_handle h, int n, const uint8_t* p1, const uint8_t* p2, uint64_t seed, const fs_outputs* traj,
+                 const fs_policy* pol, const fs_packed_traj* pk = nullptr) {
+  fsk::DevOutputs out{};
+  if (pk) {  // (fs_step_n_packed validated the buffers)
+    out.reward = pk->reward;
+    out.pk_lanes = static_cast<uint4*>(pk->lanes);
+    out.pk_final = static_cast<uint4*>(pk->final_lanes);
+  } else if (int rc = traj_outputs(h, traj, "fs_step_n", out)) {
+    return rc;
+  }
+  const uint64_t N = (uint64_t)h->n;
+  return split_launches(n, max_launch_steps(h, pk ? kMaxPackedLaunchRows : kMaxLaunchRows), [&](int j, int m) {
+    const uint64_t row = (uint64_t)j * N;  // first arena-tick row of this launch
+    StepExtras x;
+    fsk::DevOutputs t = out;
+    fsk::PolicyParams q{};
+    if (traj || pk) {
+      advance_rows(t, row);
+      x.traj = &t;
+    }
+    if (pol) {
+      q = policy_params(pol, row);
+      x.pol = &q;
+    }
+    return step_common(h, m, p1 ? p1 + row : nullptr, p2 ? p2 + row : nullptr, FS_ACT_DEVICE, seed, x);
+  });
+}
+
+// One launch's StepParams of a fused actor call (fs_step_skip_policy, fs_step_n_selfplay,
+// fs_step_skip_selfplay): `m` steps whose outputs start `row` rows into `out` (what traj_outputs gave),
+// a trajectory of rows when `rows`, else the handle's one set, overwritten
+fsk::StepParams actor_step_params(const fs_context* h, int m, const fsk::DevOutputs& out, bool rows, uint64_t row) {
+  fsk::StepParams sp = step_params(h, m);
+  sp.out = out;
+  advance_rows(sp.out, rows ? row : 0);
+  sp.out_stride_steps = rows ? 1 : 0;
+  return sp;
+}
+
+// the action-array and flags checks of the one-tick calls (`call` names the entry point)
+int check_tick_args(fs_handle h, const char* call, const uint8_t* p1, const uint8_t* p2, int flags) {
+  if (!p1 && h->cfg.p1_mode != FS_P1_BOT) return set_err(h, FS_E_INVALID, "%s: p1 actions required", call);
+  if (h->cfg.p2_mode == FS_P2_EXTERNAL && !p2)
+    return set_err(h, FS_E_INVALID, "%s: p2 actions required for FS_P2_EXTERNAL", call);
+  if (flags != FS_ACT_HOST && flags != FS_ACT_DEVICE) return set_err(h, FS_E_INVALID, "bad flags %d", flags);
+  return FS_OK;
+}
+
+// the decision cap of the fused actor calls that skip frames
+int check_max_ticks(fs_handle h, const char* call, int max_ticks) {
+  if (max_ticks < 1 || max_ticks > FS_SKIP_POLICY_MAX_TICKS)
+    return set_err(h, FS_E_INVALID, "%s: max_ticks must be 1 .. %d (got %d)", call, FS_SKIP_POLICY_MAX_TICKS,
+                   max_ticks);
+  return FS_OK;
+}
+
+// the handles fs_step_skip / fs_step_skip_policy refuse (the message names the call)
+const char* skip_unsupported(const fs_context* h) {
+  if (h->cfg.p2_mode == FS_P2_EXTERNAL)  // (also with every arena switched to the bot: the handle's kind decides)
+    return "a remote P2 (FS_P2_EXTERNAL) must answer every frame; the fused skip runs the in-game bot or an idle P2";
+  if (h->cfg.p1_mode == FS_P1_BOT) return "P1 is the bot (FS_P1_BOT): there is no agent decision to skip to";
+  if (h->cfg.frame_delay > 0)
+    return "frame_delay > 0 is not supported (the delayed queue consumes every tick's row)";
+  return nullptr;
+}
+
+// the handles fs_step_n_selfplay / fs_step_skip_selfplay refuse
+const char* selfplay_unsupported(const fs_context* h) {
+  if (h->cfg.p2_mode != FS_P2_EXTERNAL)
+    return "the second actor plays a remote P2: the handle needs FS_P2_EXTERNAL (this one runs the in-game bot or an "
+           "idle P2)";
+  if (h->cfg.p1_mode == FS_P1_BOT) return "P1 is the bot (FS_P1_BOT), not the actor";
+  if (h->cfg.frame_delay > 0) return "the actors observe undelayed frames; frame_delay > 0 is not supported";
+  if (h->p2bot_count > 0) return "some arenas' P2 is switched to the bot (fs_set_p2_mode); switch them back first";
+  return nullptr;
+}
+
+}  // namespace
 
 FS_API int fs_set_p2_mode(fs_handle h, int mode, const uint8_t* mask) {
   if (!h) return FS_E_INVALID;
@@ -554,11 +663,8 @@ FS_API int fs_set_p2_mode(fs_handle h, int mode, const uint8_t* mask) {
 
 FS_API int fs_step(fs_handle h, const uint8_t* p1_act, const uint8_t* p2_act, int flags) {
   if (!h) return FS_E_INVALID;
-  if (!p1_act && h->cfg.p1_mode != FS_P1_BOT) return set_err(h, FS_E_INVALID, "fs_step: p1 actions required");
-  if (h->cfg.p2_mode == FS_P2_EXTERNAL && !p2_act)
-    return set_err(h, FS_E_INVALID, "fs_step: p2 actions required for FS_P2_EXTERNAL");
-  if (flags != FS_ACT_HOST && flags != FS_ACT_DEVICE) return set_err(h, FS_E_INVALID, "bad flags %d", flags);
-  return step_common(h, 1, p1_act, p2_act, flags, 0, nullptr);
+  if (int rc = check_tick_args(h, "fs_step", p1_act, p2_act, flags)) return rc;
+  return step_common(h, 1, p1_act, p2_act, flags, 0);
 }
 
 FS_API int fs_step_rec(fs_handle h, const uint8_t* p1_act, const uint8_t* p2_act, int flags, void* rec) {
@@ -569,11 +675,10 @@ FS_API int fs_step_rec(fs_handle h, const uint8_t* p1_act, const uint8_t* p2_act
     const int rc = fs_step(h, p1_act, p2_act, flags);
     return rc ? rc : fs_pack_outputs(h, rec);
   }
-  if (!p1_act && h->cfg.p1_mode != FS_P1_BOT) return set_err(h, FS_E_INVALID, "fs_step_rec: p1 actions required");
-  if (h->cfg.p2_mode == FS_P2_EXTERNAL && !p2_act)
-    return set_err(h, FS_E_INVALID, "fs_step_rec: p2 actions required for FS_P2_EXTERNAL");
-  if (flags != FS_ACT_HOST && flags != FS_ACT_DEVICE) return set_err(h, FS_E_INVALID, "bad flags %d", flags);
-  return step_common(h, 1, p1_act, p2_act, flags, 0, nullptr, nullptr, nullptr, nullptr, rec);
+  if (int rc = check_tick_args(h, "fs_step_rec", p1_act, p2_act, flags)) return rc;
+  StepExtras x;
+  x.rec = rec;
+  return step_common(h, 1, p1_act, p2_act, flags, 0, x);
 }
 
 FS_API int fs_step_masked(fs_handle h, const uint8_t* p1_act, const uint8_t* p2_act, const uint8_t* active,
@@ -581,24 +686,16 @@ FS_API int fs_step_masked(fs_handle h, const uint8_t* p1_act, const uint8_t* p2_
   if (!h) return FS_E_INVALID;
   if ((!p1_act && h->cfg.p1_mode != FS_P1_BOT) || !active)
     return set_err(h, FS_E_INVALID, "fs_step_masked: p1 actions and mask required");
-  if (h->cfg.p2_mode == FS_P2_EXTERNAL && !p2_act)
-    return set_err(h, FS_E_INVALID, "fs_step_masked: p2 actions required for FS_P2_EXTERNAL");
-  if (flags != FS_ACT_HOST && flags != FS_ACT_DEVICE) return set_err(h, FS_E_INVALID, "bad flags %d", flags);
-  return step_common(h, 1, p1_act, p2_act, flags, 0, nullptr, active);
+  if (int rc = check_tick_args(h, "fs_step_masked", p1_act, p2_act, flags)) return rc;
+  StepExtras x;
+  x.active = active;
+  return step_common(h, 1, p1_act, p2_act, flags, 0, x);
 }
 
 FS_API int fs_step_skip(fs_handle h, const uint8_t* p1_act, const uint8_t* active, int flags, int max_ticks,
                         const fs_skip_out* out) {
   if (!h) return FS_E_INVALID;
-  if (h->cfg.p2_mode == FS_P2_EXTERNAL)  // (also with every arena switched to the bot: the handle's kind decides)
-    return set_err(h, FS_E_UNSUPPORTED, "fs_step_skip: a remote P2 (FS_P2_EXTERNAL) must answer every frame; the "
-                                        "fused skip runs the in-game bot or an idle P2");
-  if (h->cfg.p1_mode == FS_P1_BOT)
-    return set_err(h, FS_E_UNSUPPORTED, "fs_step_skip: P1 is the bot (FS_P1_BOT): there is no agent decision to "
-                                        "skip to");
-  if (h->cfg.frame_delay > 0)
-    return set_err(h, FS_E_UNSUPPORTED, "fs_step_skip: frame_delay > 0 is not supported (the delayed queue "
-                                        "consumes every tick's row)");
+  if (const char* why = skip_unsupported(h)) return set_err(h, FS_E_UNSUPPORTED, "fs_step_skip: %s", why);
   if (flags & ~(FS_ACT_DEVICE | FS_SKIP_RESUME)) return set_err(h, FS_E_INVALID, "fs_step_skip: bad flags %d", flags);
   if (max_ticks < 1) return set_err(h, FS_E_INVALID, "fs_step_skip: max_ticks must be >= 1 (got %d)", max_ticks);
   const bool resume = (flags & FS_SKIP_RESUME) != 0, device = (flags & FS_ACT_DEVICE) != 0;
@@ -607,19 +704,8 @@ FS_API int fs_step_skip(fs_handle h, const uint8_t* p1_act, const uint8_t* activ
   if ((rc = use_device(h))) return rc;
   const size_t N = (size_t)h->n;
   fsk::SkipParams q{};
+  q.p = step_params(h, 1);
   fsk::StepParams& sp = q.p;
-  sp.st = h->st;
-  sp.out = h->out;
-  sp.n_envs = h->n;
-  sp.n_steps = 1;
-  sp.out_stride_steps = 0;
-  sp.dense_reward = h->cfg.dense_reward;
-  sp.autoreset_mode = h->cfg.autoreset_mode;
-  sp.t0 = h->steps;
-  sp.arena_base = h->cfg.arena_base;
-  sp.p2_resets = h->cfg.p2_mode == FS_P2_BOT;
-  sp.p2_noop = h->cfg.p2_mode == FS_P2_NOOP;
-  sp.geom = h->geom;
   if (device) {
     sp.p1 = resume ? nullptr : p1_act;
     sp.active = active;
@@ -685,8 +771,7 @@ FS_API int fs_step_n_packed(fs_handle h, int n, const uint8_t* p1_act, const uin
 FS_API int fs_step_n_policy(fs_handle h, int n, const fs_policy* pol, const uint8_t* p2_act,
                             const fs_outputs* traj) {
   if (!h) return FS_E_INVALID;
-  if (!pol || !pol->w1 || !pol->b1 || !pol->w2 || !pol->b2 || !pol->w3 || !pol->b3)
-    return set_err(h, FS_E_INVALID, "fs_step_n_policy: all six weight arrays required");
+  if (!has_weights(pol)) return set_err(h, FS_E_INVALID, "fs_step_n_policy: all six weight arrays required");
   if (n <= 0) return set_err(h, FS_E_INVALID, "fs_step_n_policy: n must be > 0");
   if (h->cfg.p1_mode == FS_P1_BOT)
     return set_err(h, FS_E_UNSUPPORTED, "fs_step_n_policy: P1 is the bot (FS_P1_BOT), not the actor");
@@ -695,177 +780,70 @@ FS_API int fs_step_n_policy(fs_handle h, int n, const fs_policy* pol, const uint
   if (h->cfg.frame_delay > 0)
     return set_err(h, FS_E_UNSUPPORTED, "fs_step_n_policy: the actor observes undelayed frames; frame_delay > 0 "
                                         "is not supported");
-  return step_chunked(h, n, nullptr, p2_act, 0, traj, pol);
+  return step_chunked(h, n, nullptr, p2_act, 0, traj, pol);  // (a trajectory refusal names fs_step_n)
 }
 
-// The trajectory argument of the fused actor calls (fs_step_skip_policy, fs_step_n_selfplay,
-// fs_step_skip_selfplay): the handle's regular outputs when NULL, else the caller's buffers, every tick
-// output required and final_* in same-step auto-reset (`call` names the entry point in the message).
-static int traj_outputs(fs_handle h, const fs_outputs* traj, const char* call, fsk::DevOutputs& out) {
-  out = h->out;
-  if (!traj) return FS_OK;
-  out = fsk::DevOutputs{traj->guard,          traj->move,           traj->move_frame,  traj->position,
-                        traj->reward,         traj->terminated,     traj->truncated,   traj->frame,
-                        traj->action,         traj->hitstun,        traj->final_guard, traj->final_move,
-                        traj->final_move_frame, traj->final_position, traj->final_frame, traj->final_action,
-                        traj->final_hitstun};
-  const void* req[] = {traj->guard, traj->move,   traj->move_frame, traj->position, traj->reward,
-                       traj->terminated, traj->truncated, traj->frame, traj->action, traj->hitstun};
-  for (const void* q : req)
-    if (!q) return set_err(h, FS_E_INVALID, "%s: trajectory buffer missing", call);
-  if (h->cfg.autoreset_mode == FS_AUTORESET_SAME_STEP &&
-      (!traj->final_guard || !traj->final_move || !traj->final_move_frame || !traj->final_position ||
-       !traj->final_frame || !traj->final_action || !traj->final_hitstun))
-    return set_err(h, FS_E_INVALID, "%s: final_* trajectory buffers required in same-step autoreset", call);
-  return FS_OK;
-}
-
-// ... moved on by `row` trajectory rows: the first row of one launch of a call split by the row limit
-static void advance_rows(fsk::DevOutputs& o, uint64_t row) {
-  auto adv = [&](auto*& p, uint64_t per_row) { if (p) p += row * per_row; };
-  adv(o.guard, 2); adv(o.move, 2); adv(o.move_frame, 2); adv(o.position, 2);
-  adv(o.reward, 1); adv(o.terminated, 1); adv(o.truncated, 1); adv(o.frame, 1);
-  adv(o.action, 2); adv(o.hitstun, 2); adv(o.final_guard, 2); adv(o.final_move, 2);
-  adv(o.final_move_frame, 2); adv(o.final_position, 2); adv(o.final_frame, 1);
-  adv(o.final_action, 2); adv(o.final_hitstun, 2);
-}
-
-// the handles fs_step_skip / fs_step_skip_policy refuse (the message names the call)
-static const char* skip_unsupported(const fs_context* h) {
-  if (h->cfg.p2_mode == FS_P2_EXTERNAL)  // (also with every arena switched to the bot: the handle's kind decides)
-    return "a remote P2 (FS_P2_EXTERNAL) must answer every frame; the fused skip runs the in-game bot or an idle P2";
-  if (h->cfg.p1_mode == FS_P1_BOT) return "P1 is the bot (FS_P1_BOT): there is no agent decision to skip to";
-  if (h->cfg.frame_delay > 0)
-    return "frame_delay > 0 is not supported (the delayed queue consumes every tick's row)";
-  return nullptr;
-}
+// The three fused actor calls below have one shape, and a new one plugs in the same way: the
+// call's own refusals, traj_outputs, use_device, then split_launches over a lambda that fills the
+// kernel's parameter struct from actor_step_params and policy_params, launches, and advances h->steps.
 
 FS_API int fs_step_skip_policy(fs_handle h, int n, const fs_policy* pol, int max_ticks, const fs_outputs* traj,
                                const fs_skip_traj* skip) {
   if (!h) return FS_E_INVALID;
   if (const char* why = skip_unsupported(h)) return set_err(h, FS_E_UNSUPPORTED, "fs_step_skip_policy: %s", why);
-  if (!pol || !pol->w1 || !pol->b1 || !pol->w2 || !pol->b2 || !pol->w3 || !pol->b3)
-    return set_err(h, FS_E_INVALID, "fs_step_skip_policy: all six weight arrays required");
+  if (!has_weights(pol)) return set_err(h, FS_E_INVALID, "fs_step_skip_policy: all six weight arrays required");
   if (n < 1) return set_err(h, FS_E_INVALID, "fs_step_skip_policy: n must be >= 1 (got %d)", n);
-  if (max_ticks < 1 || max_ticks > FS_SKIP_POLICY_MAX_TICKS)
-    return set_err(h, FS_E_INVALID, "fs_step_skip_policy: max_ticks must be 1 .. %d (got %d)", FS_SKIP_POLICY_MAX_TICKS,
-                   max_ticks);
+  if (int rc = check_max_ticks(h, "fs_step_skip_policy", max_ticks)) return rc;
   fsk::DevOutputs out;
   if (int rc = traj_outputs(h, traj, "fs_step_skip_policy", out)) return rc;
-  int rc;
-  if ((rc = use_device(h))) return rc;
+  if (int rc = use_device(h)) return rc;
   const uint64_t N = (uint64_t)h->n;
-  uint64_t rows = kMaxLaunchRows;
-  if (const char* e = getenv("FOOTSIES_MAX_LAUNCH_ROWS"))  // (step_chunked's test hook)
-    rows = std::min<uint64_t>(rows, std::max<uint64_t>(1, strtoull(e, nullptr, 10)));
-  const int max_n = (int)std::max<uint64_t>(1, std::min<uint64_t>(rows / N, 0x7fffffff));
-  // consecutive launches over row ranges of the same buffers: every launch ends on decision
-  // boundaries and the sampling stream is keyed by the step counter, so the split does not show
-  for (int j = 0; j < n;) {
-    const int m = std::min(max_n, n - j);
-    const uint64_t row = traj ? (uint64_t)j * N : 0;  // first output row of this launch
-    const uint64_t row_d = (uint64_t)j * N;           // ... of the per-decision arrays
+  return split_launches(n, max_launch_steps(h, kMaxLaunchRows), [&](int j, int m) {
+    const uint64_t row_d = (uint64_t)j * N;  // first row of this launch: outputs and per-decision arrays
     fsk::SkipPolicyParams q{};
-    fsk::StepParams& sp = q.p;
-    sp.st = h->st;
-    sp.out = out;
-    advance_rows(sp.out, row);
-    sp.pol = fsk::PolicyParams{pol->w1, pol->b1, pol->w2, pol->b2, pol->w3, pol->b3,
-                               pol->actions_out ? pol->actions_out + row_d : nullptr,
-                               pol->logp_out ? pol->logp_out + row_d : nullptr, pol->seed};
-    sp.n_envs = h->n;
-    sp.n_steps = m;
-    sp.out_stride_steps = traj ? 1 : 0;
-    sp.dense_reward = h->cfg.dense_reward;
-    sp.autoreset_mode = h->cfg.autoreset_mode;
-    sp.t0 = h->steps;
-    sp.arena_base = h->cfg.arena_base;
-    sp.p2_resets = h->cfg.p2_mode == FS_P2_BOT;
-    sp.p2_noop = h->cfg.p2_mode == FS_P2_NOOP;
-    sp.geom = h->geom;
+    q.p = actor_step_params(h, m, out, traj != nullptr, row_d);
+    q.p.pol = policy_params(pol, row_d);
     q.ticks_out = skip && skip->ticks ? skip->ticks + row_d : nullptr;
     q.capped_out = skip && skip->capped ? skip->capped + row_d : nullptr;
     q.max_ticks = max_ticks;
     HIP_TRY(h, fsk::launch_step_skip_policy(q, h->cfg.float_mode, h->cfg.p2_mode, h->stream));
     h->steps += (uint64_t)m;
-    j += m;
-  }
-  return FS_OK;
-}
-
-// the handles fs_step_n_selfplay refuses
-static const char* selfplay_unsupported(const fs_context* h) {
-  if (h->cfg.p2_mode != FS_P2_EXTERNAL)
-    return "the second actor plays a remote P2: the handle needs FS_P2_EXTERNAL (this one runs the in-game bot or an "
-           "idle P2)";
-  if (h->cfg.p1_mode == FS_P1_BOT) return "P1 is the bot (FS_P1_BOT), not the actor";
-  if (h->cfg.frame_delay > 0) return "the actors observe undelayed frames; frame_delay > 0 is not supported";
-  if (h->p2bot_count > 0) return "some arenas' P2 is switched to the bot (fs_set_p2_mode); switch them back first";
-  return nullptr;
+    return (int)FS_OK;
+  });
 }
 
 FS_API int fs_step_n_selfplay(fs_handle h, int n, const fs_policy* p1, const fs_policy* p2, int flags,
                               const fs_outputs* traj) {
   if (!h) return FS_E_INVALID;
-  for (const fs_policy* pol : {p1, p2})
-    if (!pol || !pol->w1 || !pol->b1 || !pol->w2 || !pol->b2 || !pol->w3 || !pol->b3)
-      return set_err(h, FS_E_INVALID, "fs_step_n_selfplay: all six weight arrays of both actors required");
+  if (!has_weights(p1) || !has_weights(p2))
+    return set_err(h, FS_E_INVALID, "fs_step_n_selfplay: all six weight arrays of both actors required");
   if (n <= 0) return set_err(h, FS_E_INVALID, "fs_step_n_selfplay: n must be > 0");
   if (flags & ~FS_SELFPLAY_MIRROR) return set_err(h, FS_E_INVALID, "fs_step_n_selfplay: bad flags %d", flags);
   if (const char* why = selfplay_unsupported(h)) return set_err(h, FS_E_UNSUPPORTED, "fs_step_n_selfplay: %s", why);
   fsk::DevOutputs out;
   if (int rc = traj_outputs(h, traj, "fs_step_n_selfplay", out)) return rc;
-  int rc;
-  if ((rc = use_device(h))) return rc;
+  if (int rc = use_device(h)) return rc;
   const uint64_t N = (uint64_t)h->n;
-  uint64_t rows = kMaxLaunchRows;
-  if (const char* e = getenv("FOOTSIES_MAX_LAUNCH_ROWS"))  // (step_chunked's test hook)
-    rows = std::min<uint64_t>(rows, std::max<uint64_t>(1, strtoull(e, nullptr, 10)));
-  const int max_n = (int)std::max<uint64_t>(1, std::min<uint64_t>(rows / N, 0x7fffffff));
-  // step_chunked's split: consecutive launches over row ranges of the same buffers, both sampling
-  // streams keyed by the step counter each launch advances
-  for (int j = 0; j < n;) {
-    const int m = std::min(max_n, n - j);
-    const uint64_t row = traj ? (uint64_t)j * N : 0;  // first trajectory row of this launch
-    const uint64_t row_s = (uint64_t)j * N;           // ... of the actors' sample arrays
+  return split_launches(n, max_launch_steps(h, kMaxLaunchRows), [&](int j, int m) {
+    const uint64_t row = (uint64_t)j * N;  // first row of this launch: trajectory and sample arrays
     fsk::SelfPlayParams q{};
-    fsk::StepParams& sp = q.p;
-    sp.st = h->st;
-    sp.out = out;
-    advance_rows(sp.out, row);
-    auto actor = [&](const fs_policy* pol) {
-      return fsk::PolicyParams{pol->w1, pol->b1, pol->w2, pol->b2, pol->w3, pol->b3,
-                               pol->actions_out ? pol->actions_out + row_s : nullptr,
-                               pol->logp_out ? pol->logp_out + row_s : nullptr, pol->seed};
-    };
-    sp.pol = actor(p1);
-    q.pol2 = actor(p2);
+    q.p = actor_step_params(h, m, out, traj != nullptr, row);
+    q.p.pol = policy_params(p1, row);
+    q.pol2 = policy_params(p2, row);
     q.mirror = (flags & FS_SELFPLAY_MIRROR) != 0;
-    sp.n_envs = h->n;
-    sp.n_steps = m;
-    sp.out_stride_steps = traj ? 1 : 0;
-    sp.dense_reward = h->cfg.dense_reward;
-    sp.autoreset_mode = h->cfg.autoreset_mode;
-    sp.t0 = h->steps;
-    sp.arena_base = h->cfg.arena_base;
-    sp.geom = h->geom;
     HIP_TRY(h, fsk::launch_step_selfplay(q, h->cfg.float_mode, h->stream));
     h->steps += (uint64_t)m;
-    j += m;
-  }
-  return FS_OK;
+    return (int)FS_OK;
+  });
 }
 
 FS_API int fs_step_skip_selfplay(fs_handle h, int n, const fs_policy* p1, const fs_policy* p2, int flags,
                                  int max_ticks, const fs_outputs* traj, const fs_skip_traj* skip) {
   if (!h) return FS_E_INVALID;
-  for (const fs_policy* pol : {p1, p2})
-    if (!pol || !pol->w1 || !pol->b1 || !pol->w2 || !pol->b2 || !pol->w3 || !pol->b3)
-      return set_err(h, FS_E_INVALID, "fs_step_skip_selfplay: all six weight arrays of both actors required");
+  if (!has_weights(p1) || !has_weights(p2))
+    return set_err(h, FS_E_INVALID, "fs_step_skip_selfplay: all six weight arrays of both actors required");
   if (n < 1) return set_err(h, FS_E_INVALID, "fs_step_skip_selfplay: n must be >= 1 (got %d)", n);
-  if (max_ticks < 1 || max_ticks > FS_SKIP_POLICY_MAX_TICKS)
-    return set_err(h, FS_E_INVALID, "fs_step_skip_selfplay: max_ticks must be 1 .. %d (got %d)",
-                   FS_SKIP_POLICY_MAX_TICKS, max_ticks);
+  if (int rc = check_max_ticks(h, "fs_step_skip_selfplay", max_ticks)) return rc;
   if (flags & ~FS_SELFPLAY_MIRROR) return set_err(h, FS_E_INVALID, "fs_step_skip_selfplay: bad flags %d", flags);
   // P2's draw counter is (decision index) + (tick in decision << 40): injective below 2^40 decisions
   if (h->steps + (uint64_t)n >= (1ull << 40))
@@ -877,48 +855,21 @@ FS_API int fs_step_skip_selfplay(fs_handle h, int n, const fs_policy* p1, const 
                                     "exceed int32", (unsigned long long)((uint64_t)n * (uint64_t)max_ticks * N));
   fsk::DevOutputs out;
   if (int rc = traj_outputs(h, traj, "fs_step_skip_selfplay", out)) return rc;
-  int rc;
-  if ((rc = use_device(h))) return rc;
-  uint64_t rows = kMaxLaunchRows;
-  if (const char* e = getenv("FOOTSIES_MAX_LAUNCH_ROWS"))  // (step_chunked's test hook)
-    rows = std::min<uint64_t>(rows, std::max<uint64_t>(1, strtoull(e, nullptr, 10)));
-  const int max_n = (int)std::max<uint64_t>(1, std::min<uint64_t>(rows / N, 0x7fffffff));
-  // fs_step_skip_policy's split: every launch ends on decision boundaries and both sampling
-  // streams are keyed by the decision counter (and the tick within the decision)
-  for (int j = 0; j < n;) {
-    const int m = std::min(max_n, n - j);
-    const uint64_t row = traj ? (uint64_t)j * N : 0;           // first output row of this launch
-    const uint64_t row_d = (uint64_t)j * N;                    // ... of the per-decision arrays
-    const uint64_t row_t = row_d * (uint64_t)max_ticks;        // ... of P2's per-tick arrays
+  if (int rc = use_device(h)) return rc;
+  return split_launches(n, max_launch_steps(h, kMaxLaunchRows), [&](int j, int m) {
+    const uint64_t row_d = (uint64_t)j * N;  // first row of this launch: outputs and per-decision arrays
     fsk::SkipSelfPlayParams q{};
-    fsk::StepParams& sp = q.p;
-    sp.st = h->st;
-    sp.out = out;
-    advance_rows(sp.out, row);
-    auto actor = [&](const fs_policy* pol, uint64_t at) {
-      return fsk::PolicyParams{pol->w1, pol->b1, pol->w2, pol->b2, pol->w3, pol->b3,
-                               pol->actions_out ? pol->actions_out + at : nullptr,
-                               pol->logp_out ? pol->logp_out + at : nullptr, pol->seed};
-    };
-    sp.pol = actor(p1, row_d);
-    q.pol2 = actor(p2, row_t);
+    q.p = actor_step_params(h, m, out, traj != nullptr, row_d);
+    q.p.pol = policy_params(p1, row_d);
+    q.pol2 = policy_params(p2, row_d * (uint64_t)max_ticks);  // (P2's arrays are per tick)
     q.mirror = (flags & FS_SELFPLAY_MIRROR) != 0;
-    sp.n_envs = h->n;
-    sp.n_steps = m;
-    sp.out_stride_steps = traj ? 1 : 0;
-    sp.dense_reward = h->cfg.dense_reward;
-    sp.autoreset_mode = h->cfg.autoreset_mode;
-    sp.t0 = h->steps;
-    sp.arena_base = h->cfg.arena_base;
-    sp.geom = h->geom;
     q.ticks_out = skip && skip->ticks ? skip->ticks + row_d : nullptr;
     q.capped_out = skip && skip->capped ? skip->capped + row_d : nullptr;
     q.max_ticks = max_ticks;
     HIP_TRY(h, fsk::launch_step_skip_selfplay(q, h->cfg.float_mode, h->stream));
     h->steps += (uint64_t)m;
-    j += m;
-  }
-  return FS_OK;
+    return (int)FS_OK;
+  });
 }
 
 FS_API size_t fs_ppo_workspace_bytes(void) { return fsk::ppo_workspace_bytes(); }

@@ -119,6 +119,60 @@ class PolicyRollout:
             self.graph.replay()
 
 
+def _weights(actor):
+    """weight, bias of each Linear of `actor`, in order"""
+    torch = _torch()
+    return [t for m in actor if isinstance(m, torch.nn.Linear) for t in (m.weight, m.bias)]
+
+
+def _actor_params(sim, actor):
+    """The six fp32 tensors of an in-kernel actor on sim's device (the module's own where it already
+    holds them so)."""
+    torch = _torch()
+    w = _weights(actor)
+    shapes = [tuple(t.shape) for t in w[::2]]
+    if shapes != [(64, N_FEATURES), (64, 64), (N_ACTIONS, 64)]:
+        raise ValueError("the fused actor is 8 -> 64 -> 64 -> 8; got %s" % (shapes,))
+    with torch.no_grad():
+        return [t.detach().to(device=sim.device, dtype=torch.float32).contiguous() for t in w]
+
+
+def _copy_weights(params, actor):
+    torch = _torch()
+    with torch.no_grad():
+        for dst, src in zip(params, _weights(actor)):
+            dst.copy_(src)
+
+
+def _buffer(given, shape, dtype, device):
+    """A sample array argument: allocated when None, kept when given, False = off."""
+    return _torch().empty(shape, dtype=dtype, device=device) if given is None else given
+
+
+def _ptr(t):
+    return None if t is False else t.data_ptr()
+
+
+def _policy(params, seed, actions, logp):
+    """fs_policy of an actor's six tensors, its seed and its sample arrays (False = off)."""
+    w1, b1, w2, b2, w3, b3 = (t.data_ptr() for t in params)
+    return _abi.fs_policy(w1=w1, b1=b1, w2=w2, b2=b2, w3=w3, b3=b3, seed=seed, actions_out=_ptr(actions),
+                          logp_out=_ptr(logp))
+
+
+def _skip_counts(n, max_ticks):
+    n, max_ticks = int(n), int(max_ticks)
+    if n < 1:
+        raise ValueError("rollout_skipped: n must be >= 1, got %d" % n)
+    if not 1 <= max_ticks <= _abi.FS_SKIP_POLICY_MAX_TICKS:
+        raise ValueError("rollout_skipped: max_ticks must be 1 .. %d, got %d" % (_abi.FS_SKIP_POLICY_MAX_TICKS, max_ticks))
+    return n, max_ticks
+
+
+def _byref(struct):
+    return None if struct is None else C.byref(struct)
+
+
 class FusedPolicyRollout:
     """C5 in one launch per block of ticks: `actor` (the make_actor shape, 8-64-64-8 with tanh)
     is evaluated in bf16 inside the simulator kernel, P1's action drawn from its softmax by
@@ -126,46 +180,33 @@ class FusedPolicyRollout:
     was created with (bot, noop, or `p2_actions` [n][N] per call for external)."""
 
     def __init__(self, sim, actor, seed=0):
-        torch = _torch()
-        lin = [m for m in actor if isinstance(m, torch.nn.Linear)]
-        shapes = [tuple(m.weight.shape) for m in lin]
-        if shapes != [(64, N_FEATURES), (64, 64), (N_ACTIONS, 64)]:
-            raise ValueError("the fused actor is 8 -> 64 -> 64 -> 8; got %s" % (shapes,))
+        self.params = _actor_params(sim, actor)
         self.sim, self.seed = sim, int(seed) & (2**64 - 1)
         self.last_capped = None  # rollout_skipped: the last call's capped flags
-        with torch.no_grad():
-            self.params = [t.detach().to(device=sim.device, dtype=torch.float32).contiguous()
-                           for m in lin for t in (m.weight, m.bias)]
 
     def refresh(self, actor):
         """Copy new actor weights in (after an optimiser step); the buffers stay put."""
+        _copy_weights(self.params, actor)
+
+    def _decision_buffers(self, n, actions, logp, ticks, capped):
+        """rollout_skipped's [n][N] arrays by decision and the fs_skip_traj of the last two"""
         torch = _torch()
-        lin = [m for m in actor if isinstance(m, torch.nn.Linear)]
-        with torch.no_grad():
-            for dst, src in zip(self.params, [t for m in lin for t in (m.weight, m.bias)]):
-                dst.copy_(src)
+        shape, dev = (n, self.sim.num_envs), self.sim.device
+        actions, logp = _buffer(actions, shape, torch.uint8, dev), _buffer(logp, shape, torch.float32, dev)
+        ticks, capped = _buffer(ticks, shape, torch.int32, dev), _buffer(capped, shape, torch.uint8, dev)
+        return actions, logp, ticks, capped, _abi.fs_skip_traj(ticks=_ptr(ticks), capped=_ptr(capped))
 
     def rollout(self, n, actions=None, logp=None, p2_actions=None, trajectory=None):
         """n policy-driven ticks in one launch.  `actions` (uint8) / `logp` (float32) [n][N]
         device tensors receive P1's samples (allocated when None; pass False to skip one).
         Returns (actions, logp)."""
         torch = _torch()
-        N, dev = self.sim.num_envs, self.sim.device
-        if actions is None:
-            actions = torch.empty((n, N), dtype=torch.uint8, device=dev)
-        if logp is None:
-            logp = torch.empty((n, N), dtype=torch.float32, device=dev)
-        w = self.params
-        pol = _abi.fs_policy(w1=w[0].data_ptr(), b1=w[1].data_ptr(), w2=w[2].data_ptr(), b2=w[3].data_ptr(),
-                             w3=w[4].data_ptr(), b3=w[5].data_ptr(), seed=self.seed,
-                             actions_out=actions.data_ptr() if actions is not False else None,
-                             logp_out=logp.data_ptr() if logp is not False else None)
-        t = None
-        if trajectory is not None:
-            t = _abi.fs_outputs(**{k: trajectory[k].data_ptr() for k in _abi.OUTPUT_SPEC if k in trajectory})
+        shape, dev = (n, self.sim.num_envs), self.sim.device
+        actions, logp = _buffer(actions, shape, torch.uint8, dev), _buffer(logp, shape, torch.float32, dev)
+        pol = _policy(self.params, self.seed, actions, logp)
         check(lib().fs_step_n_policy(self.sim.handle, int(n), C.byref(pol),
                                      None if p2_actions is None else C.c_void_p(p2_actions.data_ptr()),
-                                     None if t is None else C.byref(t)), self.sim.handle)
+                                     _byref(_abi.trajectory_outputs(trajectory))), self.sim.handle)
         return actions, logp
 
     def rollout_skipped(self, n, actions=None, logp=None, ticks=None, capped=None, trajectory=None,
@@ -178,33 +219,11 @@ class FusedPolicyRollout:
         allocated when None, pass False to skip one.  `trajectory` rows hold each decision's last
         tick with the summed reward.  The handle's P2 must be the bot or idle.  Returns (actions,
         logp, ticks); the `capped` array of the call stays in ``last_capped``."""
-        n, max_ticks = int(n), int(max_ticks)
-        if n < 1:
-            raise ValueError("rollout_skipped: n must be >= 1, got %d" % n)
-        if not 1 <= max_ticks <= _abi.FS_SKIP_POLICY_MAX_TICKS:
-            raise ValueError("rollout_skipped: max_ticks must be 1 .. %d, got %d" % (_abi.FS_SKIP_POLICY_MAX_TICKS, max_ticks))
-        torch = _torch()
-        N, dev = self.sim.num_envs, self.sim.device
-        if actions is None:
-            actions = torch.empty((n, N), dtype=torch.uint8, device=dev)
-        if logp is None:
-            logp = torch.empty((n, N), dtype=torch.float32, device=dev)
-        if ticks is None:
-            ticks = torch.empty((n, N), dtype=torch.int32, device=dev)
-        if capped is None:
-            capped = torch.empty((n, N), dtype=torch.uint8, device=dev)
-        w = self.params
-        pol = _abi.fs_policy(w1=w[0].data_ptr(), b1=w[1].data_ptr(), w2=w[2].data_ptr(), b2=w[3].data_ptr(),
-                             w3=w[4].data_ptr(), b3=w[5].data_ptr(), seed=self.seed,
-                             actions_out=actions.data_ptr() if actions is not False else None,
-                             logp_out=logp.data_ptr() if logp is not False else None)
-        skip = _abi.fs_skip_traj(ticks=ticks.data_ptr() if ticks is not False else None,
-                                 capped=capped.data_ptr() if capped is not False else None)
-        t = None
-        if trajectory is not None:
-            t = _abi.fs_outputs(**{k: trajectory[k].data_ptr() for k in _abi.OUTPUT_SPEC if k in trajectory})
+        n, max_ticks = _skip_counts(n, max_ticks)
+        actions, logp, ticks, capped, skip = self._decision_buffers(n, actions, logp, ticks, capped)
+        pol = _policy(self.params, self.seed, actions, logp)
         check(lib().fs_step_skip_policy(self.sim.handle, n, C.byref(pol), max_ticks,
-                                        None if t is None else C.byref(t), C.byref(skip)), self.sim.handle)
+                                        _byref(_abi.trajectory_outputs(trajectory)), C.byref(skip)), self.sim.handle)
         self.last_capped = capped
         return actions, logp, ticks
 
@@ -238,9 +257,9 @@ class FusedSelfPlayRollout(FusedPolicyRollout):
 
     def __init__(self, sim, actor, opponent=None, seed=0, opponent_seed=None, mirror=True):
         super().__init__(sim, actor, seed=seed)
-        # (cloned: `params` may be the module's own tensors when it already sits on the device in fp32,
+        # (cloned: the tensors may be the module's own when it already sits on the device in fp32,
         # and the opponent has to stay what it was while the learner moves on)
-        self.params2 = [p.clone() for p in FusedPolicyRollout(sim, actor if opponent is None else opponent).params]
+        self.params2 = [p.clone() for p in _actor_params(sim, actor if opponent is None else opponent)]
         if opponent_seed is None:
             opponent_seed = self.seed ^ 0x9E3779B97F4A7C15  # (never equal to seed)
         self.opponent_seed = int(opponent_seed) & (2**64 - 1)
@@ -248,11 +267,10 @@ class FusedSelfPlayRollout(FusedPolicyRollout):
 
     def refresh_opponent(self, actor):
         """Copy new weights into the opponent's buffers, which stay put."""
-        torch = _torch()
-        lin = [m for m in actor if isinstance(m, torch.nn.Linear)]
-        with torch.no_grad():
-            for dst, src in zip(self.params2, [t for m in lin for t in (m.weight, m.bias)]):
-                dst.copy_(src)
+        _copy_weights(self.params2, actor)
+
+    def _flags(self):
+        return _abi.FS_SELFPLAY_MIRROR if self.mirror else 0
 
     def rollout(self, n, actions=None, logp=None, p2_actions=None, p2_logp=None, trajectory=None):
         """n ticks in one launch, both fighters sampled in-kernel.  `actions` / `logp` receive P1's
@@ -260,27 +278,15 @@ class FusedSelfPlayRollout(FusedPolicyRollout):
         uint8 / float32 device tensors, allocated when None; pass False to skip one).  Rewards and
         `trajectory` are P1's, as in FusedPolicyRollout.  Returns (actions, logp, p2_actions, p2_logp)."""
         torch = _torch()
-        N, dev = self.sim.num_envs, self.sim.device
         n = int(n)
-        out = []
-        for given, dtype in ((actions, torch.uint8), (logp, torch.float32), (p2_actions, torch.uint8),
-                             (p2_logp, torch.float32)):
-            out.append(torch.empty((n, N), dtype=dtype, device=dev) if given is None else given)
-
-        def actor(w, seed, a, lp):
-            return _abi.fs_policy(w1=w[0].data_ptr(), b1=w[1].data_ptr(), w2=w[2].data_ptr(), b2=w[3].data_ptr(),
-                                  w3=w[4].data_ptr(), b3=w[5].data_ptr(), seed=seed,
-                                  actions_out=a.data_ptr() if a is not False else None,
-                                  logp_out=lp.data_ptr() if lp is not False else None)
-        p1 = actor(self.params, self.seed, out[0], out[1])
-        p2 = actor(self.params2, self.opponent_seed, out[2], out[3])
-        t = None
-        if trajectory is not None:
-            t = _abi.fs_outputs(**{k: trajectory[k].data_ptr() for k in _abi.OUTPUT_SPEC if k in trajectory})
-        check(lib().fs_step_n_selfplay(self.sim.handle, n, C.byref(p1), C.byref(p2),
-                                       _abi.FS_SELFPLAY_MIRROR if self.mirror else 0,
-                                       None if t is None else C.byref(t)), self.sim.handle)
-        return tuple(out)
+        shape, dev = (n, self.sim.num_envs), self.sim.device
+        out = tuple(_buffer(given, shape, dtype, dev) for given, dtype in (
+            (actions, torch.uint8), (logp, torch.float32), (p2_actions, torch.uint8), (p2_logp, torch.float32)))
+        p1 = _policy(self.params, self.seed, out[0], out[1])
+        p2 = _policy(self.params2, self.opponent_seed, out[2], out[3])
+        check(lib().fs_step_n_selfplay(self.sim.handle, n, C.byref(p1), C.byref(p2), self._flags(),
+                                       _byref(_abi.trajectory_outputs(trajectory))), self.sim.handle)
+        return out
 
     def rollout_skipped(self, n, actions=None, logp=None, ticks=None, capped=None, p2_actions=False, p2_logp=False,
                         trajectory=None, max_ticks=_abi.FS_SKIP_DEFAULT_MAX_TICKS):
@@ -294,41 +300,15 @@ class FusedSelfPlayRollout(FusedPolicyRollout):
         pass None to have one allocated (entries of ticks that did not run are left as they were) or a
         tensor of that shape.  Returns (actions, logp, ticks); `last_capped` holds the call's capped
         flags and `last_p2` the (p2_actions, p2_logp) pair (False where off)."""
-        n, max_ticks = int(n), int(max_ticks)
-        if n < 1:
-            raise ValueError("rollout_skipped: n must be >= 1, got %d" % n)
-        if not 1 <= max_ticks <= _abi.FS_SKIP_POLICY_MAX_TICKS:
-            raise ValueError("rollout_skipped: max_ticks must be 1 .. %d, got %d" % (_abi.FS_SKIP_POLICY_MAX_TICKS, max_ticks))
+        n, max_ticks = _skip_counts(n, max_ticks)
+        actions, logp, ticks, capped, skip = self._decision_buffers(n, actions, logp, ticks, capped)
         torch = _torch()
-        N, dev = self.sim.num_envs, self.sim.device
-        if actions is None:
-            actions = torch.empty((n, N), dtype=torch.uint8, device=dev)
-        if logp is None:
-            logp = torch.empty((n, N), dtype=torch.float32, device=dev)
-        if ticks is None:
-            ticks = torch.empty((n, N), dtype=torch.int32, device=dev)
-        if capped is None:
-            capped = torch.empty((n, N), dtype=torch.uint8, device=dev)
-        if p2_actions is None:
-            p2_actions = torch.empty((n, max_ticks, N), dtype=torch.uint8, device=dev)
-        if p2_logp is None:
-            p2_logp = torch.empty((n, max_ticks, N), dtype=torch.float32, device=dev)
-
-        def actor(w, seed, a, lp):
-            return _abi.fs_policy(w1=w[0].data_ptr(), b1=w[1].data_ptr(), w2=w[2].data_ptr(), b2=w[3].data_ptr(),
-                                  w3=w[4].data_ptr(), b3=w[5].data_ptr(), seed=seed,
-                                  actions_out=a.data_ptr() if a is not False else None,
-                                  logp_out=lp.data_ptr() if lp is not False else None)
-        p1 = actor(self.params, self.seed, actions, logp)
-        p2 = actor(self.params2, self.opponent_seed, p2_actions, p2_logp)
-        skip = _abi.fs_skip_traj(ticks=ticks.data_ptr() if ticks is not False else None,
-                                 capped=capped.data_ptr() if capped is not False else None)
-        t = None
-        if trajectory is not None:
-            t = _abi.fs_outputs(**{k: trajectory[k].data_ptr() for k in _abi.OUTPUT_SPEC if k in trajectory})
-        check(lib().fs_step_skip_selfplay(self.sim.handle, n, C.byref(p1), C.byref(p2),
-                                          _abi.FS_SELFPLAY_MIRROR if self.mirror else 0, max_ticks,
-                                          None if t is None else C.byref(t), C.byref(skip)), self.sim.handle)
+        shape, dev = (n, max_ticks, self.sim.num_envs), self.sim.device
+        p2_actions, p2_logp = _buffer(p2_actions, shape, torch.uint8, dev), _buffer(p2_logp, shape, torch.float32, dev)
+        p1 = _policy(self.params, self.seed, actions, logp)
+        p2 = _policy(self.params2, self.opponent_seed, p2_actions, p2_logp)
+        check(lib().fs_step_skip_selfplay(self.sim.handle, n, C.byref(p1), C.byref(p2), self._flags(), max_ticks,
+                                          _byref(_abi.trajectory_outputs(trajectory)), C.byref(skip)), self.sim.handle)
         self.last_capped = capped
         self.last_p2 = (p2_actions, p2_logp)
         return actions, logp, ticks

@@ -365,14 +365,13 @@ class FootsiesSim:
         for name, a in (("p1", p1), ("p2", p2)):
             if a is not None:
                 self._check_device(a, name, torch.uint8, n * self.num_envs)
-        t = None
         if trajectory is not None:
             for k in _abi.OUTPUT_SPEC:
                 if k in trajectory:
                     dt, cols = _abi.OUTPUT_SPEC[k]
                     self._check_device(trajectory[k], "trajectory[%r]" % k, getattr(torch, _TORCH_DTYPES[dt]),
                                        n * self.num_envs * cols)
-            t = _abi.fs_outputs(**{k: trajectory[k].data_ptr() for k in _abi.OUTPUT_SPEC if k in trajectory})
+        t = _abi.trajectory_outputs(trajectory)
         check(lib().fs_step_n(self._h, int(n), None if p1 is None else C.c_void_p(p1.data_ptr()),
                               None if p2 is None else C.c_void_p(p2.data_ptr()), int(action_seed) & (2**64 - 1),
                               None if t is None else C.byref(t)), self._h)
