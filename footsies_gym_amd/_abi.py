@@ -46,7 +46,11 @@ FS_KERNEL_PACKED = 4
 FS_KERNEL_SKIP_POLICY = 16
 FS_KERNEL_SELFPLAY = 32
 FS_KERNEL_SKIP_SELFPLAY = 64
+FS_KERNEL_SELFPLAY_POOL = 128
+FS_KERNEL_SKIP_SELFPLAY_POOL = 256
 FS_SELFPLAY_MIRROR = 1
+FS_SELFPLAY_GROUP = 128
+FS_SELFPLAY_POOL_MAX = 256
 FS_SKIP_POLICY_MAX_TICKS = 4096
 FS_PACKED_LANE_BYTES = 16
 FS_PPO_ACTOR_PARAMS = 5256
@@ -136,6 +140,13 @@ class fs_policy(C.Structure):
     ]
 
 
+class fs_policy_pool(C.Structure):
+    _fields_ = [
+        ("weights", C.c_void_p), ("n_slots", C.c_int), ("slot", C.c_void_p), ("seed", C.c_uint64),
+        ("actions_out", C.c_void_p), ("logp_out", C.c_void_p),
+    ]
+
+
 class fs_mlp(C.Structure):
     _fields_ = [("w1", C.c_void_p), ("b1", C.c_void_p), ("w2", C.c_void_p), ("b2", C.c_void_p), ("w3", C.c_void_p),
                 ("b3", C.c_void_p)]
@@ -199,6 +210,10 @@ LIB_FUNCTIONS = {
                                      C.POINTER(fs_outputs)]),
     "fs_step_skip_selfplay": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(fs_policy), C.POINTER(fs_policy), C.c_int,
                                         C.c_int, C.POINTER(fs_outputs), C.POINTER(fs_skip_traj)]),
+    "fs_step_n_selfplay_pool": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(fs_policy), C.POINTER(fs_policy_pool),
+                                          C.c_int, C.POINTER(fs_outputs)]),
+    "fs_step_skip_selfplay_pool": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(fs_policy), C.POINTER(fs_policy_pool),
+                                             C.c_int, C.c_int, C.POINTER(fs_outputs), C.POINTER(fs_skip_traj)]),
     "fs_ppo_workspace_bytes": (C.c_size_t, []),
     "fs_ppo_eval": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.POINTER(fs_mlp), C.POINTER(fs_mlp),
                               C.c_void_p, C.c_void_p, C.c_void_p]),

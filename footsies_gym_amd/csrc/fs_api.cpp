@@ -786,6 +786,7 @@ FS_API int fs_step_n_policy(fs_handle h, int n, const fs_policy* pol, const uint
 // The three fused actor calls below have one shape, and a new one plugs in the same way: the
 // call's own refusals, traj_outputs, use_device, then split_launches over a lambda that fills the
 // kernel's parameter struct from actor_step_params and policy_params, launches, and advances h->steps.
+// (The two self-play calls share theirs with their pool forms: step_n_selfplay, step_skip_selfplay.)
 
 FS_API int fs_step_skip_policy(fs_handle h, int n, const fs_policy* pol, int max_ticks, const fs_outputs* traj,
                                const fs_skip_traj* skip) {
@@ -812,16 +813,42 @@ FS_API int fs_step_skip_policy(fs_handle h, int n, const fs_policy* pol, int max
   });
 }
 
-FS_API int fs_step_n_selfplay(fs_handle h, int n, const fs_policy* p1, const fs_policy* p2, int flags,
-                              const fs_outputs* traj) {
-  if (!h) return FS_E_INVALID;
-  if (!has_weights(p1) || !has_weights(p2))
-    return set_err(h, FS_E_INVALID, "fs_step_n_selfplay: all six weight arrays of both actors required");
-  if (n <= 0) return set_err(h, FS_E_INVALID, "fs_step_n_selfplay: n must be > 0");
-  if (flags & ~FS_SELFPLAY_MIRROR) return set_err(h, FS_E_INVALID, "fs_step_n_selfplay: bad flags %d", flags);
-  if (const char* why = selfplay_unsupported(h)) return set_err(h, FS_E_UNSUPPORTED, "fs_step_n_selfplay: %s", why);
+// Both self-play calls and their pool forms run through one function each: `p2` carries P2's seed and
+// sample arrays (and, without a pool, its weights); `pool`, when given, the weights per arena group.
+// The entry points check their own actor arguments first and name themselves in `call`.
+
+namespace {
+
+// a pool argument in full: FS_OK, or the refusal set on h
+int check_pool(fs_handle h, const char* call, const fs_policy_pool* pool) {
+  if (!pool || !pool->weights || !pool->slot)
+    return set_err(h, FS_E_INVALID, "%s: the pool, its weights and its slot array are required", call);
+  if (pool->n_slots < 1 || pool->n_slots > FS_SELFPLAY_POOL_MAX)
+    return set_err(h, FS_E_INVALID, "%s: n_slots must be 1 .. %d (got %d)", call, FS_SELFPLAY_POOL_MAX, pool->n_slots);
+  return FS_OK;
+}
+
+// P2's seed and sample arrays of a pool call as the fs_policy the shared code reads (no weights: the
+// kernel takes them from the pool)
+fs_policy pool_actor(const fs_policy_pool* pool) {
+  fs_policy p{};
+  p.seed = pool->seed;
+  p.actions_out = pool->actions_out;
+  p.logp_out = pool->logp_out;
+  return p;
+}
+
+fsk::PoolParams pool_params(const fs_policy_pool* pool) {
+  return fsk::PoolParams{pool->weights, pool->slot, pool->n_slots};
+}
+
+int step_n_selfplay(fs_handle h, const char* call, int n, const fs_policy* p1, const fs_policy& p2,
+                    const fsk::PoolParams* pool, int flags, const fs_outputs* traj) {
+  if (n <= 0) return set_err(h, FS_E_INVALID, "%s: n must be > 0", call);
+  if (flags & ~FS_SELFPLAY_MIRROR) return set_err(h, FS_E_INVALID, "%s: bad flags %d", call, flags);
+  if (const char* why = selfplay_unsupported(h)) return set_err(h, FS_E_UNSUPPORTED, "%s: %s", call, why);
   fsk::DevOutputs out;
-  if (int rc = traj_outputs(h, traj, "fs_step_n_selfplay", out)) return rc;
+  if (int rc = traj_outputs(h, traj, call, out)) return rc;
   if (int rc = use_device(h)) return rc;
   const uint64_t N = (uint64_t)h->n;
   return split_launches(n, max_launch_steps(h, kMaxLaunchRows), [&](int j, int m) {
@@ -829,12 +856,64 @@ FS_API int fs_step_n_selfplay(fs_handle h, int n, const fs_policy* p1, const fs_
     fsk::SelfPlayParams q{};
     q.p = actor_step_params(h, m, out, traj != nullptr, row);
     q.p.pol = policy_params(p1, row);
-    q.pol2 = policy_params(p2, row);
+    q.pol2 = policy_params(&p2, row);
     q.mirror = (flags & FS_SELFPLAY_MIRROR) != 0;
-    HIP_TRY(h, fsk::launch_step_selfplay(q, h->cfg.float_mode, h->stream));
+    HIP_TRY(h, fsk::launch_step_selfplay(q, pool, h->cfg.float_mode, h->stream));
     h->steps += (uint64_t)m;
     return (int)FS_OK;
   });
+}
+
+int step_skip_selfplay(fs_handle h, const char* call, int n, const fs_policy* p1, const fs_policy& p2,
+                       const fsk::PoolParams* pool, int flags, int max_ticks, const fs_outputs* traj,
+                       const fs_skip_traj* skip) {
+  if (n < 1) return set_err(h, FS_E_INVALID, "%s: n must be >= 1 (got %d)", call, n);
+  if (int rc = check_max_ticks(h, call, max_ticks)) return rc;
+  if (flags & ~FS_SELFPLAY_MIRROR) return set_err(h, FS_E_INVALID, "%s: bad flags %d", call, flags);
+  // P2's draw counter is (decision index) + (tick in decision << 40): injective below 2^40 decisions
+  if (h->steps + (uint64_t)n >= (1ull << 40))
+    return set_err(h, FS_E_INVALID, "%s: fs_steps_taken + n must stay below 2^40", call);
+  if (const char* why = selfplay_unsupported(h)) return set_err(h, FS_E_UNSUPPORTED, "%s: %s", call, why);
+  const uint64_t N = (uint64_t)h->n;
+  if ((p2.actions_out || p2.logp_out) && (uint64_t)n * (uint64_t)max_ticks * N > 0x7fffffffull)
+    return set_err(h, FS_E_INVALID, "%s: n * max_ticks * N = %llu entries of P2's sample arrays exceed int32", call,
+                   (unsigned long long)((uint64_t)n * (uint64_t)max_ticks * N));
+  fsk::DevOutputs out;
+  if (int rc = traj_outputs(h, traj, call, out)) return rc;
+  if (int rc = use_device(h)) return rc;
+  return split_launches(n, max_launch_steps(h, kMaxLaunchRows), [&](int j, int m) {
+    const uint64_t row_d = (uint64_t)j * N;  // first row of this launch: outputs and per-decision arrays
+    fsk::SkipSelfPlayParams q{};
+    q.p = actor_step_params(h, m, out, traj != nullptr, row_d);
+    q.p.pol = policy_params(p1, row_d);
+    q.pol2 = policy_params(&p2, row_d * (uint64_t)max_ticks);  // (P2's arrays are per tick)
+    q.mirror = (flags & FS_SELFPLAY_MIRROR) != 0;
+    q.ticks_out = skip && skip->ticks ? skip->ticks + row_d : nullptr;
+    q.capped_out = skip && skip->capped ? skip->capped + row_d : nullptr;
+    q.max_ticks = max_ticks;
+    HIP_TRY(h, fsk::launch_step_skip_selfplay(q, pool, h->cfg.float_mode, h->stream));
+    h->steps += (uint64_t)m;
+    return (int)FS_OK;
+  });
+}
+
+}  // namespace
+
+FS_API int fs_step_n_selfplay(fs_handle h, int n, const fs_policy* p1, const fs_policy* p2, int flags,
+                              const fs_outputs* traj) {
+  if (!h) return FS_E_INVALID;
+  if (!has_weights(p1) || !has_weights(p2))
+    return set_err(h, FS_E_INVALID, "fs_step_n_selfplay: all six weight arrays of both actors required");
+  return step_n_selfplay(h, "fs_step_n_selfplay", n, p1, *p2, nullptr, flags, traj);
+}
+
+FS_API int fs_step_n_selfplay_pool(fs_handle h, int n, const fs_policy* p1, const fs_policy_pool* pool, int flags,
+                                   const fs_outputs* traj) {
+  if (!h) return FS_E_INVALID;
+  if (!has_weights(p1)) return set_err(h, FS_E_INVALID, "fs_step_n_selfplay_pool: all six weight arrays of P1's actor required");
+  if (int rc = check_pool(h, "fs_step_n_selfplay_pool", pool)) return rc;
+  const fsk::PoolParams pp = pool_params(pool);
+  return step_n_selfplay(h, "fs_step_n_selfplay_pool", n, p1, pool_actor(pool), &pp, flags, traj);
 }
 
 FS_API int fs_step_skip_selfplay(fs_handle h, int n, const fs_policy* p1, const fs_policy* p2, int flags,
@@ -842,34 +921,17 @@ FS_API int fs_step_skip_selfplay(fs_handle h, int n, const fs_policy* p1, const 
   if (!h) return FS_E_INVALID;
   if (!has_weights(p1) || !has_weights(p2))
     return set_err(h, FS_E_INVALID, "fs_step_skip_selfplay: all six weight arrays of both actors required");
-  if (n < 1) return set_err(h, FS_E_INVALID, "fs_step_skip_selfplay: n must be >= 1 (got %d)", n);
-  if (int rc = check_max_ticks(h, "fs_step_skip_selfplay", max_ticks)) return rc;
-  if (flags & ~FS_SELFPLAY_MIRROR) return set_err(h, FS_E_INVALID, "fs_step_skip_selfplay: bad flags %d", flags);
-  // P2's draw counter is (decision index) + (tick in decision << 40): injective below 2^40 decisions
-  if (h->steps + (uint64_t)n >= (1ull << 40))
-    return set_err(h, FS_E_INVALID, "fs_step_skip_selfplay: fs_steps_taken + n must stay below 2^40");
-  if (const char* why = selfplay_unsupported(h)) return set_err(h, FS_E_UNSUPPORTED, "fs_step_skip_selfplay: %s", why);
-  const uint64_t N = (uint64_t)h->n;
-  if ((p2->actions_out || p2->logp_out) && (uint64_t)n * (uint64_t)max_ticks * N > 0x7fffffffull)
-    return set_err(h, FS_E_INVALID, "fs_step_skip_selfplay: n * max_ticks * N = %llu entries of P2's sample arrays "
-                                    "exceed int32", (unsigned long long)((uint64_t)n * (uint64_t)max_ticks * N));
-  fsk::DevOutputs out;
-  if (int rc = traj_outputs(h, traj, "fs_step_skip_selfplay", out)) return rc;
-  if (int rc = use_device(h)) return rc;
-  return split_launches(n, max_launch_steps(h, kMaxLaunchRows), [&](int j, int m) {
-    const uint64_t row_d = (uint64_t)j * N;  // first row of this launch: outputs and per-decision arrays
-    fsk::SkipSelfPlayParams q{};
-    q.p = actor_step_params(h, m, out, traj != nullptr, row_d);
-    q.p.pol = policy_params(p1, row_d);
-    q.pol2 = policy_params(p2, row_d * (uint64_t)max_ticks);  // (P2's arrays are per tick)
-    q.mirror = (flags & FS_SELFPLAY_MIRROR) != 0;
-    q.ticks_out = skip && skip->ticks ? skip->ticks + row_d : nullptr;
-    q.capped_out = skip && skip->capped ? skip->capped + row_d : nullptr;
-    q.max_ticks = max_ticks;
-    HIP_TRY(h, fsk::launch_step_skip_selfplay(q, h->cfg.float_mode, h->stream));
-    h->steps += (uint64_t)m;
-    return (int)FS_OK;
-  });
+  return step_skip_selfplay(h, "fs_step_skip_selfplay", n, p1, *p2, nullptr, flags, max_ticks, traj, skip);
+}
+
+FS_API int fs_step_skip_selfplay_pool(fs_handle h, int n, const fs_policy* p1, const fs_policy_pool* pool, int flags,
+                                      int max_ticks, const fs_outputs* traj, const fs_skip_traj* skip) {
+  if (!h) return FS_E_INVALID;
+  if (!has_weights(p1))
+    return set_err(h, FS_E_INVALID, "fs_step_skip_selfplay_pool: all six weight arrays of P1's actor required");
+  if (int rc = check_pool(h, "fs_step_skip_selfplay_pool", pool)) return rc;
+  const fsk::PoolParams pp = pool_params(pool);
+  return step_skip_selfplay(h, "fs_step_skip_selfplay_pool", n, p1, pool_actor(pool), &pp, flags, max_ticks, traj, skip);
 }
 
 FS_API size_t fs_ppo_workspace_bytes(void) { return fsk::ppo_workspace_bytes(); }
@@ -1206,9 +1268,13 @@ FS_API const char* fs_step_kernel(fs_handle h, int n_steps, int flags) {
   if (h && n_steps > 0 && flags == FS_KERNEL_SKIP_POLICY)
     return skip_unsupported(h) ? nullptr : fsk::step_skip_policy_kernel_name(h->cfg.float_mode, h->cfg.p2_mode);
   if (h && n_steps > 0 && flags == FS_KERNEL_SELFPLAY)
-    return selfplay_unsupported(h) ? nullptr : fsk::step_selfplay_kernel_name(h->cfg.float_mode);
+    return selfplay_unsupported(h) ? nullptr : fsk::step_selfplay_kernel_name(h->cfg.float_mode, false);
   if (h && n_steps > 0 && flags == FS_KERNEL_SKIP_SELFPLAY)
-    return selfplay_unsupported(h) ? nullptr : fsk::step_skip_selfplay_kernel_name(h->cfg.float_mode);
+    return selfplay_unsupported(h) ? nullptr : fsk::step_skip_selfplay_kernel_name(h->cfg.float_mode, false);
+  if (h && n_steps > 0 && flags == FS_KERNEL_SELFPLAY_POOL)
+    return selfplay_unsupported(h) ? nullptr : fsk::step_selfplay_kernel_name(h->cfg.float_mode, true);
+  if (h && n_steps > 0 && flags == FS_KERNEL_SKIP_SELFPLAY_POOL)
+    return selfplay_unsupported(h) ? nullptr : fsk::step_skip_selfplay_kernel_name(h->cfg.float_mode, true);
   if (!h || n_steps <= 0 || (flags & ~(FS_KERNEL_HASHED | FS_KERNEL_POLICY | FS_KERNEL_PACKED))) return nullptr;
   return fsk::step_kernel_name((flags & FS_KERNEL_POLICY) != 0, (flags & FS_KERNEL_HASHED) != 0, n_steps, h->n,
                                h->cfg.float_mode, variant(h), h->geom, (flags & FS_KERNEL_PACKED) != 0,

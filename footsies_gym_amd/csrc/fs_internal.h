@@ -139,6 +139,22 @@ struct SkipSelfPlayParams {
   int mirror;           // FS_SELFPLAY_MIRROR
 };
 
+// fs_step_n_selfplay_pool / fs_step_skip_selfplay_pool: P2's weights of the two launches above chosen per
+// block (kBlock / 2 = FS_SELFPLAY_GROUP arenas) from a pool of actors; pol2's six weight pointers are unused
+struct PoolParams {
+  const float* weights;  // [n_slots][FS_PPO_ACTOR_PARAMS], a slot = w1 | b1 | w2 | b2 | w3 | b3
+  const uint8_t* slot;   // [blocks of the launch]: block b stages slot min(slot[b], n_slots - 1)
+  int n_slots;           // >= 1
+};
+struct SelfPlayPoolParams {
+  SelfPlayParams q;
+  PoolParams pool;
+};
+struct SkipSelfPlayPoolParams {
+  SkipSelfPlayParams q;
+  PoolParams pool;
+};
+
 struct ResetParams {
   DevState st;
   DevOutputs out;
@@ -179,10 +195,11 @@ hipError_t launch_step_skip(const SkipParams& q, int float_mode, int p2_mode, hi
 hipError_t launch_step_skip_policy(const SkipPolicyParams& q, int float_mode, int p2_mode, hipStream_t s);
 const char* step_skip_policy_kernel_name(int float_mode, int p2_mode);
 // (FS_P2_EXTERNAL handles with no arena switched to the bot; fs_step_n_selfplay refuses the others)
-hipError_t launch_step_selfplay(const SelfPlayParams& q, int float_mode, hipStream_t s);
-const char* step_selfplay_kernel_name(int float_mode);
-hipError_t launch_step_skip_selfplay(const SkipSelfPlayParams& q, int float_mode, hipStream_t s);
-const char* step_skip_selfplay_kernel_name(int float_mode);
+// pool: null for one opponent (q.pol2's weights), else the pool kernel with P2's weights per block
+hipError_t launch_step_selfplay(const SelfPlayParams& q, const PoolParams* pool, int float_mode, hipStream_t s);
+const char* step_selfplay_kernel_name(int float_mode, bool pool);
+hipError_t launch_step_skip_selfplay(const SkipSelfPlayParams& q, const PoolParams* pool, int float_mode, hipStream_t s);
+const char* step_skip_selfplay_kernel_name(int float_mode, bool pool);
 hipError_t launch_reset(const ResetParams& p, int float_mode, hipStream_t s);
 hipError_t launch_set_p2(const DevState& st, int bot, const uint8_t* mask, int n, hipStream_t s);
 hipError_t launch_hash_actions(int n_envs, int n_steps, uint64_t seed, uint64_t t0, uint64_t arena_base, uint8_t* p1,

@@ -2585,8 +2585,10 @@ __global__ __launch_bounds__(256) void k_step_skip_policy(SkipPolicyParams q) {
 // read from a second LDS image every tick (PolicyWeightsLds): a second resident set would end two
 // waves per SIMD, which 65 536 arenas are.  Lanes past the last arena stay in for the actors, a
 // wholly idle wave leaves (as POL).
-template <class C>
-__device__ __forceinline__ void selfplay_body(const SelfPlayParams& q) {
+// POOL (k_step_n_selfplay_pool): P2's image is staged from the block's slot of `pool` (pool_policy), i.e.
+// per FS_SELFPLAY_GROUP arenas; nothing after the staging differs.
+template <class C, bool POOL = false>
+__device__ __forceinline__ void selfplay_body(const SelfPlayParams& q, const PoolParams& pool = {}) {
   constexpr int P2 = C::P2;
   static_assert(C::TP == kTabLds && P2 == FS_P2_EXTERNAL, "fs_step_n_selfplay: a remote P2, played by the second actor");
   const StepParams& p = q.p;
@@ -2598,7 +2600,11 @@ __device__ __forceinline__ void selfplay_body(const SelfPlayParams& q) {
   load_lane<P2>(L, p.st, a, k);
   if constexpr (C::GEOM) L.f.y = reinterpret_cast<const float*>(p.st.posy)[2 * a + (int)k];
   stage_policy(p.pol);
-  stage_policy<true>(q.pol2, sPol2);
+  if constexpr (POOL) {
+    if (threadIdx.x >= 64 && threadIdx.x < 128) stage_policy<true>(pool_policy(q.pol2, pool), sPol2);
+  } else {
+    stage_policy<true>(q.pol2, sPol2);
+  }
   stage_tables<false>();
   if ((l & ~63) >= 2 * p.n_envs) return;  // the whole wave is past the last arena
   L.te = next_tick_entry<false>(L.f);
@@ -2649,6 +2655,13 @@ __global__ __launch_bounds__(256) void k_step_n_selfplay(SelfPlayParams q) {
   if (q.p.geom) selfplay_body<TickCfg<FM, FS_P2_EXTERNAL, kPolicy, kGeom>>(q);
   else selfplay_body<TickCfg<FM, FS_P2_EXTERNAL, kPolicy>>(q);
 }
+// fs_step_n_selfplay_pool: the same body, P2's weights per block
+template <int FM>
+__global__ __launch_bounds__(256) void k_step_n_selfplay_pool(SelfPlayPoolParams q) {
+  static_assert(kBlock / 2 == FS_SELFPLAY_GROUP, "a group of the pool is one block's arenas");
+  if (q.q.p.geom) selfplay_body<TickCfg<FM, FS_P2_EXTERNAL, kPolicy, kGeom>, true>(q.q, q.pool);
+  else selfplay_body<TickCfg<FM, FS_P2_EXTERNAL, kPolicy>, true>(q.q, q.pool);
+}
 }  // namespace selfplay
 
 // fs_step_skip_selfplay: p.n_steps agent decisions per arena with the second actor playing P2 on
@@ -2669,8 +2682,9 @@ __global__ __launch_bounds__(256) void k_step_n_selfplay(SelfPlayParams q) {
 // is split or which arenas share a wave.  P2's optional sample arrays are [n][max_ticks][N].
 // Both actors' fragments are read from their LDS images every wave tick: the per-arena counters
 // and the reward sum take the registers a resident set would (two waves per SIMD: 256 VGPRs).
-template <class C>
-__device__ __forceinline__ void skip_selfplay_body(const SkipSelfPlayParams& q) {
+// POOL (k_step_skip_pool_selfplay): as in selfplay_body.
+template <class C, bool POOL = false>
+__device__ __forceinline__ void skip_selfplay_body(const SkipSelfPlayParams& q, const PoolParams& pool = {}) {
   constexpr int P2 = C::P2;
   static_assert(C::TP == kTabLds && P2 == FS_P2_EXTERNAL, "fs_step_skip_selfplay: a remote P2, played by the second actor");
   const StepParams& p = q.p;
@@ -2682,7 +2696,11 @@ __device__ __forceinline__ void skip_selfplay_body(const SkipSelfPlayParams& q) 
   load_lane<P2>(L, p.st, a, k);
   if constexpr (C::GEOM) L.f.y = reinterpret_cast<const float*>(p.st.posy)[2 * a + (int)k];
   stage_policy(p.pol);
-  stage_policy<true>(q.pol2, sPol2);
+  if constexpr (POOL) {
+    if (threadIdx.x >= 64 && threadIdx.x < 128) stage_policy<true>(pool_policy(q.pol2, pool), sPol2);
+  } else {
+    stage_policy<true>(q.pol2, sPol2);
+  }
   stage_tables<false>();
   if ((l & ~63) >= 2 * p.n_envs) return;  // the whole wave is past the last arena
   L.te = next_tick_entry<false>(L.f);
@@ -2765,6 +2783,14 @@ template <int FM>
 __global__ __launch_bounds__(256) void k_step_skip_selfplay(SkipSelfPlayParams q) {
   if (q.p.geom) skip_selfplay_body<TickCfg<FM, FS_P2_EXTERNAL, kPolicy, kGeom>>(q);
   else skip_selfplay_body<TickCfg<FM, FS_P2_EXTERNAL, kPolicy>>(q);
+}
+// fs_step_skip_selfplay_pool: the same body, P2's weights per block.  (Named k_step_skip_pool_selfplay, not
+// ..._selfplay_pool: tests/test_selfplay_skip_resources.py counts the two kernels above by the substring
+// "k_step_skip_selfplay".)
+template <int FM>
+__global__ __launch_bounds__(256) void k_step_skip_pool_selfplay(SkipSelfPlayPoolParams q) {
+  if (q.q.p.geom) skip_selfplay_body<TickCfg<FM, FS_P2_EXTERNAL, kPolicy, kGeom>, true>(q.q, q.pool);
+  else skip_selfplay_body<TickCfg<FM, FS_P2_EXTERNAL, kPolicy>, true>(q.q, q.pool);
 }
 }  // namespace selfplay
 
@@ -3216,33 +3242,47 @@ const char* step_skip_policy_kernel_name(int float_mode, int p2_mode) {
 }
 
 // (named after every other kernel; the wave-priority slices as launch_choice sets them for k_step_n_policy)
-hipError_t launch_step_selfplay(const SelfPlayParams& q_in, int float_mode, hipStream_t s) {
+hipError_t launch_step_selfplay(const SelfPlayParams& q_in, const PoolParams* pool, int float_mode, hipStream_t s) {
   const StepParams& p = q_in.p;
   SelfPlayParams q = q_in;
   q.p.prio = launch_choice(true, false, p.n_steps, p.n_envs, FS_P2_EXTERNAL, p.geom != 0, false, p.autoreset_mode).prio;
   const dim3 grid = grid_for(2 * p.n_envs), block(kBlock);
-  if (float_mode == FS_FLOAT_DOUBLE) hipLaunchKernelGGL(selfplay::k_step_n_selfplay<FS_FLOAT_DOUBLE>, grid, block, 0, s, q);
-  else hipLaunchKernelGGL(selfplay::k_step_n_selfplay<FS_FLOAT_STRICT32>, grid, block, 0, s, q);
+  if (pool) {
+    const SelfPlayPoolParams qp{q, *pool};
+    if (float_mode == FS_FLOAT_DOUBLE) hipLaunchKernelGGL(selfplay::k_step_n_selfplay_pool<FS_FLOAT_DOUBLE>, grid, block, 0, s, qp);
+    else hipLaunchKernelGGL(selfplay::k_step_n_selfplay_pool<FS_FLOAT_STRICT32>, grid, block, 0, s, qp);
+  } else if (float_mode == FS_FLOAT_DOUBLE) {
+    hipLaunchKernelGGL(selfplay::k_step_n_selfplay<FS_FLOAT_DOUBLE>, grid, block, 0, s, q);
+  } else {
+    hipLaunchKernelGGL(selfplay::k_step_n_selfplay<FS_FLOAT_STRICT32>, grid, block, 0, s, q);
+  }
   return hipGetLastError();
 }
 
-const char* step_selfplay_kernel_name(int float_mode) {
+const char* step_selfplay_kernel_name(int float_mode, bool pool) {
   static thread_local char buf[64];
-  snprintf(buf, sizeof buf, "fsk::selfplay::k_step_n_selfplay<%d>", float_mode == FS_FLOAT_DOUBLE);
+  snprintf(buf, sizeof buf, "fsk::selfplay::k_step_n_selfplay%s<%d>", pool ? "_pool" : "", float_mode == FS_FLOAT_DOUBLE);
   return buf;
 }
 
 // (named after every other kernel)
-hipError_t launch_step_skip_selfplay(const SkipSelfPlayParams& q, int float_mode, hipStream_t s) {
+hipError_t launch_step_skip_selfplay(const SkipSelfPlayParams& q, const PoolParams* pool, int float_mode, hipStream_t s) {
   const dim3 grid = grid_for(2 * q.p.n_envs), block(kBlock);
-  if (float_mode == FS_FLOAT_DOUBLE) hipLaunchKernelGGL(selfplay::k_step_skip_selfplay<FS_FLOAT_DOUBLE>, grid, block, 0, s, q);
-  else hipLaunchKernelGGL(selfplay::k_step_skip_selfplay<FS_FLOAT_STRICT32>, grid, block, 0, s, q);
+  if (pool) {
+    const SkipSelfPlayPoolParams qp{q, *pool};
+    if (float_mode == FS_FLOAT_DOUBLE) hipLaunchKernelGGL(selfplay::k_step_skip_pool_selfplay<FS_FLOAT_DOUBLE>, grid, block, 0, s, qp);
+    else hipLaunchKernelGGL(selfplay::k_step_skip_pool_selfplay<FS_FLOAT_STRICT32>, grid, block, 0, s, qp);
+  } else if (float_mode == FS_FLOAT_DOUBLE) {
+    hipLaunchKernelGGL(selfplay::k_step_skip_selfplay<FS_FLOAT_DOUBLE>, grid, block, 0, s, q);
+  } else {
+    hipLaunchKernelGGL(selfplay::k_step_skip_selfplay<FS_FLOAT_STRICT32>, grid, block, 0, s, q);
+  }
   return hipGetLastError();
 }
 
-const char* step_skip_selfplay_kernel_name(int float_mode) {
+const char* step_skip_selfplay_kernel_name(int float_mode, bool pool) {
   static thread_local char buf[64];
-  snprintf(buf, sizeof buf, "fsk::selfplay::k_step_skip_selfplay<%d>", float_mode == FS_FLOAT_DOUBLE);
+  snprintf(buf, sizeof buf, "fsk::selfplay::k_step_skip_%sselfplay<%d>", pool ? "pool_" : "", float_mode == FS_FLOAT_DOUBLE);
   return buf;
 }
 

@@ -92,6 +92,22 @@ __device__ __forceinline__ void stage_policy(const PolicyParams& P, bf16x8 (&sPo
   sPol[kPolA3b][l] = b;
 }
 
+// The pool kernels' P2 (PoolParams): `P` with the weights of this block's slot, slot[blockIdx.x] clamped
+// to the pool, so no byte of `slot` takes a read outside `weights`.  One block-uniform byte; read by the
+// staging wave alone (stage_policy<true>).
+__device__ __forceinline__ PolicyParams pool_policy(PolicyParams P, const PoolParams& pool) {
+  static_assert(64 * 8 + 64 + 64 * 64 + 64 + 8 * 64 + 8 == FS_PPO_ACTOR_PARAMS, "a slot is the six arrays, packed");
+  const int s = min((int)pool.slot[blockIdx.x], pool.n_slots - 1);
+  const float* w = pool.weights + (size_t)s * FS_PPO_ACTOR_PARAMS;
+  P.w1 = w;
+  P.b1 = P.w1 + 64 * 8;
+  P.w2 = P.b1 + 64;
+  P.b2 = P.w2 + 64 * 64;
+  P.w3 = P.b2 + 64;
+  P.b3 = P.w3 + 8 * 64;
+  return P;
+}
+
 // e^x on v_exp_f32 (2^x, ~1 ulp) with no denormal range fix-up: the results feed a softmax
 __device__ __forceinline__ float fast_exp(float x) { return __builtin_amdgcn_exp2f(x * 1.4426950408889634f); }
 

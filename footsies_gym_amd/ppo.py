@@ -33,7 +33,8 @@ import time
 
 from . import _abi
 from ._lib import check, lib
-from .rollout import N_ACTIONS, N_FEATURES, FusedPolicyRollout, FusedSelfPlayRollout, make_actor, obs_features
+from .rollout import (N_ACTIONS, N_FEATURES, FusedPolicyRollout, FusedSelfPlayRollout, OpponentPool, make_actor,
+                      obs_features)
 
 
 def _torch():
@@ -356,6 +357,18 @@ class PPOTrainer:
     holds the frame-skip and the self-play entries.  `frame_skip` is implied; `self_play=True` stays
     per tick and still refuses `frame_skip=True`.
 
+    `opponent_pool=K` (K >= 2, with either self-play mode): P2 plays a pool of up to K past snapshots
+    instead of one (rollout.OpponentPool; fs_step_n_selfplay_pool / fs_step_skip_selfplay_pool, still one
+    launch per rollout).  The pool starts with the initial actor, every `opponent_refresh`-th update pushes
+    the learner's weights (over the oldest snapshot once K are held), and every collect() draws a fresh
+    assignment of snapshots to groups of 128 arenas: with probability `opponent_latest` the newest, else
+    uniform over the pool (OpponentPool.assign of (seed, collect count), keyed by the global group index, so
+    G ranks over shards draw what one rank over all arenas would).  `stats` gains `pool_filled` and, of the
+    last rollout, `pool_episodes` and `pool_wins` ([K] int64 by slot: rows with `terminated`, and those of
+    them with reward > 0 -- decision rows under "decisions"); `opponent_age` is measured against the newest
+    snapshot.  Under `group=` these three entries are rank-local.  `opponent_pool=None` is the
+    single-opponent trainer, bit for bit.
+
     Data-parallel (`group`: a torch.distributed process group, or "default" for the default one;
     SURVEY.md §8(e)): one trainer per rank, each over its own FootsiesSim (a ShardedSim's handle:
     its arena_base keys the actor's sampling stream, so ranks roll out different arenas), all with
@@ -369,7 +382,7 @@ class PPOTrainer:
     def __init__(self, sim, actor=None, critic=None, horizon=128, gamma=0.99, lam=0.95, epochs=2, minibatches=4,
                  lr=3e-4, clip=0.2, vf_coef=0.5, ent_coef=0.01, seed=0, old_logp="behaviour", learner="hip",
                  kl_ticks=None, learner_precision="split_bf16", group=None, frame_skip=False, max_skip_ticks=64,
-                 self_play=False, opponent_refresh=1, opponent_seed=None):
+                 self_play=False, opponent_refresh=1, opponent_seed=None, opponent_pool=None, opponent_latest=0.5):
         torch = _torch()
         decisions = isinstance(self_play, str)
         if decisions and self_play != "decisions":
@@ -383,6 +396,17 @@ class PPOTrainer:
         frame_skip = frame_skip or decisions
         if self_play and int(opponent_refresh) < 1:
             raise ValueError("opponent_refresh must be >= 1, got %r" % (opponent_refresh,))
+        if opponent_pool is not None:
+            if not self_play:
+                raise ValueError("opponent_pool needs self_play=True or 'decisions'")
+            if not 2 <= int(opponent_pool) <= _abi.FS_SELFPLAY_POOL_MAX:
+                raise ValueError("opponent_pool must be 2 .. %d snapshots (None: one opponent), got %r" % (
+                    _abi.FS_SELFPLAY_POOL_MAX, opponent_pool))
+            if not 0.0 <= float(opponent_latest) <= 1.0:
+                raise ValueError("opponent_latest must be within [0, 1], got %r" % (opponent_latest,))
+            if getattr(sim, "arena_base", 0) % _abi.FS_SELFPLAY_GROUP:
+                raise ValueError("opponent_pool needs a sim whose arena_base is a multiple of %d, got %d" % (
+                    _abi.FS_SELFPLAY_GROUP, sim.arena_base))
         if old_logp not in ("behaviour", "fp32"):
             raise ValueError("old_logp must be 'behaviour' or 'fp32'")
         if frame_skip and not 1 <= int(max_skip_ticks) <= _abi.FS_SKIP_POLICY_MAX_TICKS:
@@ -406,7 +430,13 @@ class PPOTrainer:
             self._join_ranks(sim.num_envs)
         self.self_play, self.opponent_refresh = bool(self_play), int(opponent_refresh)
         self._updates = self._opponent_taken = 0  # updates done; the count at which the opponent was copied
-        if self.self_play:  # (opponent=None: a copy of the actor as it is now)
+        self.pool, self.opponent_latest, self._pool_seed = None, float(opponent_latest), int(seed)
+        self._collects = 0  # rollouts so far: the pool assignment's iteration
+        if opponent_pool is not None:  # the first snapshot: the actor as it is now
+            self.pool = OpponentPool(sim, int(opponent_pool), self.actor)
+            self.rollout = FusedSelfPlayRollout(sim, self.actor, seed=seed, opponent_seed=opponent_seed, mirror=True,
+                                                pool=self.pool)
+        elif self.self_play:  # (opponent=None: a copy of the actor as it is now)
             self.rollout = FusedSelfPlayRollout(sim, self.actor, seed=seed, opponent_seed=opponent_seed, mirror=True)
         else:
             self.rollout = FusedPolicyRollout(sim, self.actor, seed=seed)
@@ -458,10 +488,17 @@ class PPOTrainer:
         as [T][N] device tensors (the trajectory's own buffers)."""
         torch = _torch()
         first = self._next_first if self._next_first is not None else obs_features(self.sim.outputs())
+        pool = {}
+        if self.pool is not None:  # this rollout's snapshot per arena group
+            self.slots = self.pool.assign(self._collects, self.opponent_latest, self._pool_seed)
+            pool = {"slots": self.slots}
+        self._collects += 1
         if self.frame_skip:  # a row per agent decision: its last tick, the rewards of its ticks summed
             # (self_play="decisions": the same call on FusedSelfPlayRollout, P2's samples not stored)
             self.rollout.rollout_skipped(self.horizon, self.actions, self.logp, self.ticks, self.capped,
-                                         trajectory=self.traj, max_ticks=self.max_skip_ticks)
+                                         trajectory=self.traj, max_ticks=self.max_skip_ticks, **pool)
+        elif self.self_play and self.pool is not None:
+            self.rollout.rollout(self.horizon, self.actions, self.logp, False, False, trajectory=self.traj, **pool)
         elif self.self_play:  # P2's samples are not learnt from: not stored
             self.rollout.rollout(self.horizon, self.actions, self.logp, False, False, trajectory=self.traj)
         else:
@@ -586,8 +623,12 @@ class PPOTrainer:
                 self.opt.step()
         self.rollout.refresh(self.actor)
         self._updates += 1
+        pool_stats = self._pool_stats(rewards, dones) if self.pool is not None else {}  # (before the push)
         if self.self_play and self._updates % self.opponent_refresh == 0:  # (every rank at the same update)
-            self.rollout.refresh_opponent(self.actor)
+            if self.pool is not None:
+                self.pool.push(self.actor)
+            else:
+                self.rollout.refresh_opponent(self.actor)
             self._opponent_taken = self._updates
         if self._grad is not None:
             pg, vf, ent = lm[0].clone(), lm[1].clone(), lm[2].clone()
@@ -605,6 +646,19 @@ class PPOTrainer:
             self.stats["capped"] = self.capped.sum()
         if self.self_play:  # updates since the opponent's weights were copied from the learner
             self.stats["opponent_age"] = torch.tensor(self._updates - self._opponent_taken)
+        if self.pool is not None:
+            self.stats.update(pool_stats, pool_filled=torch.tensor(self.pool.filled))
+
+    def _pool_stats(self, rewards, dones):
+        """Per slot of the pool, over the last rollout's rows (this rank's): episodes that ended and those of
+        them P1 won (the reference's win counter: `terminated` with reward > 0), as [K] int64 tensors."""
+        torch = _torch()
+        arena_slot = self.slots.long().repeat_interleave(_abi.FS_SELFPLAY_GROUP)[:self.sim.num_envs]
+        arena_slot = arena_slot.clamp_(max=self.pool.capacity - 1)
+        done = dones != 0
+        zero = torch.zeros(self.pool.capacity, dtype=torch.int64, device=dones.device)
+        return {"pool_episodes": zero.index_add(0, arena_slot, done.sum(0)),
+                "pool_wins": zero.index_add(0, arena_slot, (done & (rewards > 0)).sum(0))}
 
     def iterate(self):
         self.update(*self.collect())

@@ -19,6 +19,11 @@ asked once per decision and each arena skipping its own frames as under Footsies
 or any learned opponent of the same shape, with both fighters reacting every tick inside one launch;
 its ``rollout_skipped`` (fs_step_skip_selfplay) runs agent decisions instead, P1's actor asked once per
 decision and the opponent on every tick, the ones P1 skips included.
+
+:class:`OpponentPool` holds several opponent snapshots in one device buffer, and
+``FusedSelfPlayRollout(sim, actor, pool=pool)`` plays them all in the same one launch
+(fs_step_n_selfplay_pool / fs_step_skip_selfplay_pool): each group of 128 consecutive arenas meets the
+snapshot its byte of ``slots`` names.
 """
 import ctypes as C
 
@@ -129,12 +134,17 @@ def _actor_params(sim, actor):
     """The six fp32 tensors of an in-kernel actor on sim's device (the module's own where it already
     holds them so)."""
     torch = _torch()
-    w = _weights(actor)
-    shapes = [tuple(t.shape) for t in w[::2]]
-    if shapes != [(64, N_FEATURES), (64, 64), (N_ACTIONS, 64)]:
-        raise ValueError("the fused actor is 8 -> 64 -> 64 -> 8; got %s" % (shapes,))
+    w = _weights(_checked_actor(actor))
     with torch.no_grad():
         return [t.detach().to(device=sim.device, dtype=torch.float32).contiguous() for t in w]
+
+
+def _checked_actor(actor):
+    """`actor`, or ValueError unless it has the in-kernel actor's shape."""
+    shapes = [tuple(t.shape) for t in _weights(actor)[::2]]
+    if shapes != [(64, N_FEATURES), (64, 64), (N_ACTIONS, 64)]:
+        raise ValueError("the fused actor is 8 -> 64 -> 64 -> 8; got %s" % (shapes,))
+    return actor
 
 
 def _copy_weights(params, actor):
@@ -255,11 +265,24 @@ class FusedSelfPlayRollout(FusedPolicyRollout):
     equal weights, equal seeds and `mirror` both fighters would act identically for as long as the
     game stays symmetric."""
 
-    def __init__(self, sim, actor, opponent=None, seed=0, opponent_seed=None, mirror=True):
+    def __new__(cls, sim=None, actor=None, *args, pool=None, **kwargs):
+        # FusedSelfPlayRollout(sim, actor, pool=...) is a FusedPoolSelfPlayRollout, whose rollout calls take
+        # `slots`; without a pool this class is untouched, its methods' signatures included
+        if pool is not None and cls is FusedSelfPlayRollout:
+            cls = FusedPoolSelfPlayRollout
+        return super().__new__(cls)
+
+    def __init__(self, sim, actor, opponent=None, seed=0, opponent_seed=None, mirror=True, pool=None):
         super().__init__(sim, actor, seed=seed)
-        # (cloned: the tensors may be the module's own when it already sits on the device in fp32,
-        # and the opponent has to stay what it was while the learner moves on)
-        self.params2 = [p.clone() for p in _actor_params(sim, actor if opponent is None else opponent)]
+        self.pool = pool
+        if pool is None:
+            # (cloned: the tensors may be the module's own when it already sits on the device in fp32,
+            # and the opponent has to stay what it was while the learner moves on)
+            self.params2 = [p.clone() for p in _actor_params(sim, actor if opponent is None else opponent)]
+        elif opponent is not None:
+            raise ValueError("FusedSelfPlayRollout takes `opponent` or `pool`, not both")
+        elif pool.sim is not sim:
+            raise ValueError("the pool belongs to another sim")
         if opponent_seed is None:
             opponent_seed = self.seed ^ 0x9E3779B97F4A7C15  # (never equal to seed)
         self.opponent_seed = int(opponent_seed) & (2**64 - 1)
@@ -267,25 +290,37 @@ class FusedSelfPlayRollout(FusedPolicyRollout):
 
     def refresh_opponent(self, actor):
         """Copy new weights into the opponent's buffers, which stay put."""
+        if self.pool is not None:
+            raise ValueError("this rollout plays a pool: push(actor) to it instead")
         _copy_weights(self.params2, actor)
 
     def _flags(self):
         return _abi.FS_SELFPLAY_MIRROR if self.mirror else 0
+
+    def _opponent(self, call, slots, p2_actions, p2_logp):
+        """(the library's `call`, its P2 argument): fs_policy of the one opponent, or with `slots` the pool
+        form of the call and its fs_policy_pool"""
+        if self.pool is None:
+            return getattr(lib(), call), _policy(self.params2, self.opponent_seed, p2_actions, p2_logp)
+        return getattr(lib(), call + "_pool"), self.pool.argument(slots, self.opponent_seed, p2_actions, p2_logp)
 
     def rollout(self, n, actions=None, logp=None, p2_actions=None, p2_logp=None, trajectory=None):
         """n ticks in one launch, both fighters sampled in-kernel.  `actions` / `logp` receive P1's
         samples, `p2_actions` / `p2_logp` P2's (its sampled index, before swap_left_right; [n][N]
         uint8 / float32 device tensors, allocated when None; pass False to skip one).  Rewards and
         `trajectory` are P1's, as in FusedPolicyRollout.  Returns (actions, logp, p2_actions, p2_logp)."""
+        return self._rollout(None, n, actions, logp, p2_actions, p2_logp, trajectory)
+
+    def _rollout(self, slots, n, actions, logp, p2_actions, p2_logp, trajectory):
         torch = _torch()
         n = int(n)
         shape, dev = (n, self.sim.num_envs), self.sim.device
         out = tuple(_buffer(given, shape, dtype, dev) for given, dtype in (
             (actions, torch.uint8), (logp, torch.float32), (p2_actions, torch.uint8), (p2_logp, torch.float32)))
         p1 = _policy(self.params, self.seed, out[0], out[1])
-        p2 = _policy(self.params2, self.opponent_seed, out[2], out[3])
-        check(lib().fs_step_n_selfplay(self.sim.handle, n, C.byref(p1), C.byref(p2), self._flags(),
-                                       _byref(_abi.trajectory_outputs(trajectory))), self.sim.handle)
+        call, p2 = self._opponent("fs_step_n_selfplay", slots, out[2], out[3])
+        check(call(self.sim.handle, n, C.byref(p1), C.byref(p2), self._flags(),
+                   _byref(_abi.trajectory_outputs(trajectory))), self.sim.handle)
         return out
 
     def rollout_skipped(self, n, actions=None, logp=None, ticks=None, capped=None, p2_actions=False, p2_logp=False,
@@ -300,15 +335,145 @@ class FusedSelfPlayRollout(FusedPolicyRollout):
         pass None to have one allocated (entries of ticks that did not run are left as they were) or a
         tensor of that shape.  Returns (actions, logp, ticks); `last_capped` holds the call's capped
         flags and `last_p2` the (p2_actions, p2_logp) pair (False where off)."""
+        return self._rollout_skipped(None, n, actions, logp, ticks, capped, p2_actions, p2_logp, trajectory, max_ticks)
+
+    def _rollout_skipped(self, slots, n, actions, logp, ticks, capped, p2_actions, p2_logp, trajectory, max_ticks):
         n, max_ticks = _skip_counts(n, max_ticks)
         actions, logp, ticks, capped, skip = self._decision_buffers(n, actions, logp, ticks, capped)
         torch = _torch()
         shape, dev = (n, max_ticks, self.sim.num_envs), self.sim.device
         p2_actions, p2_logp = _buffer(p2_actions, shape, torch.uint8, dev), _buffer(p2_logp, shape, torch.float32, dev)
         p1 = _policy(self.params, self.seed, actions, logp)
-        p2 = _policy(self.params2, self.opponent_seed, p2_actions, p2_logp)
-        check(lib().fs_step_skip_selfplay(self.sim.handle, n, C.byref(p1), C.byref(p2), self._flags(), max_ticks,
-                                          _byref(_abi.trajectory_outputs(trajectory)), C.byref(skip)), self.sim.handle)
+        call, p2 = self._opponent("fs_step_skip_selfplay", slots, p2_actions, p2_logp)
+        check(call(self.sim.handle, n, C.byref(p1), C.byref(p2), self._flags(), max_ticks,
+                   _byref(_abi.trajectory_outputs(trajectory)), C.byref(skip)), self.sim.handle)
         self.last_capped = capped
         self.last_p2 = (p2_actions, p2_logp)
         return actions, logp, ticks
+
+
+class FusedPoolSelfPlayRollout(FusedSelfPlayRollout):
+    """FusedSelfPlayRollout against an OpponentPool (what ``FusedSelfPlayRollout(sim, actor, pool=pool)``
+    builds): the same two launches, fs_step_n_selfplay_pool / fs_step_skip_selfplay_pool, with P2's weights
+    chosen per group of 128 consecutive arenas.  `slots` is the uint8 device tensor of each group's slot
+    (OpponentPool.assign, or any [ceil(N / 128)] tensor; a value past the pool's capacity plays the last
+    slot).  Every arena's results are bit for bit those of the single-opponent call with its group's
+    weights.  Everything else is FusedSelfPlayRollout's."""
+
+    def rollout(self, n, actions=None, logp=None, p2_actions=None, p2_logp=None, trajectory=None, slots=None):
+        return self._rollout(slots, n, actions, logp, p2_actions, p2_logp, trajectory)
+
+    def rollout_skipped(self, n, actions=None, logp=None, ticks=None, capped=None, p2_actions=False, p2_logp=False,
+                        trajectory=None, max_ticks=_abi.FS_SKIP_DEFAULT_MAX_TICKS, slots=None):
+        return self._rollout_skipped(slots, n, actions, logp, ticks, capped, p2_actions, p2_logp, trajectory, max_ticks)
+
+
+def pool_groups(num_envs):
+    """Groups of FS_SELFPLAY_GROUP arenas in a handle of `num_envs` (the last may be partial)."""
+    return (int(num_envs) + _abi.FS_SELFPLAY_GROUP - 1) // _abi.FS_SELFPLAY_GROUP
+
+
+def _mix64(x):
+    """policy_uniform's splitmix64 finaliser on a numpy uint64 array (csrc/fs_policy.h)."""
+    import numpy as np
+    with np.errstate(over="ignore"):
+        x = x + np.uint64(0x9E3779B97F4A7C15)
+        x = (x ^ (x >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+        x = (x ^ (x >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+    return x ^ (x >> np.uint64(31))
+
+
+def pool_assignment(seed, iteration, first_group, groups, filled, newest, latest=0.5):
+    """The slot of each of `groups` consecutive arena groups from global group `first_group` on, as a numpy
+    uint8 array: a pure function of its arguments, counter-based like the kernels' policy_uniform.
+    Group G draws two 24-bit integers v_k = mix64(seed ^ G * 0x9E3779B97F4A7C15 ^ (iteration + (k << 40)) *
+    0xD1B54A32D192ED03) >> 40, k = 0, 1 (policy_uniform's bits on counter iteration + (k << 40)): it plays
+    `newest` when v_0 < latest * 2^24, else slot (v_1 * filled) >> 24, uniform over the filled slots
+    0 .. filled - 1."""
+    import numpy as np
+    if not 0.0 <= float(latest) <= 1.0:
+        raise ValueError("latest must be within [0, 1], got %r" % (latest,))
+    if not (1 <= int(filled) <= _abi.FS_SELFPLAY_POOL_MAX and 0 <= int(newest) < int(filled)):
+        raise ValueError("filled must be 1 .. %d and newest below it, got %r, %r" % (
+            _abi.FS_SELFPLAY_POOL_MAX, filled, newest))
+    m = 2**64 - 1
+    g = np.arange(int(first_group), int(first_group) + int(groups), dtype=np.uint64)
+    with np.errstate(over="ignore"):
+        key = np.uint64(int(seed) & m) ^ (g * np.uint64(0x9E3779B97F4A7C15))
+        v = [_mix64(key ^ np.uint64(((int(iteration) + (k << 40)) * 0xD1B54A32D192ED03) & m)) >> np.uint64(40)
+             for k in (0, 1)]
+    drawn = (v[1] * np.uint64(int(filled))) >> np.uint64(24)
+    return np.where(v[0] < np.uint64(int(round(float(latest) * 2**24))), np.uint64(int(newest)), drawn).astype(np.uint8)
+
+
+class OpponentPool:
+    """Up to `capacity` (1 .. 256) opponent snapshots for FusedSelfPlayRollout(sim, actor, pool=...), in one
+    [capacity][5256] fp32 device buffer that stays put (``weights``; a slot is w1 | b1 | w2 | b2 | w3 | b3 in
+    torch layouts, FS_PPO_ACTOR_PARAMS floats).  `actor`, when given, is pushed as the first snapshot."""
+
+    def __init__(self, sim, capacity, actor=None):
+        torch = _torch()
+        capacity = int(capacity)
+        if not 1 <= capacity <= _abi.FS_SELFPLAY_POOL_MAX:
+            raise ValueError("OpponentPool: capacity must be 1 .. %d, got %d" % (_abi.FS_SELFPLAY_POOL_MAX, capacity))
+        self.sim, self.capacity = sim, capacity
+        self.weights = torch.zeros((capacity, _abi.FS_PPO_ACTOR_PARAMS), dtype=torch.float32, device=sim.device)
+        self.pushes = 0  # snapshots taken so far: slot pushes % capacity is the next one's
+        if actor is not None:
+            self.push(actor)
+
+    @property
+    def filled(self):
+        """Slots that hold a snapshot: 0 .. filled - 1."""
+        return min(self.pushes, self.capacity)
+
+    @property
+    def newest(self):
+        """The slot last pushed (None before the first push)."""
+        return (self.pushes - 1) % self.capacity if self.pushes else None
+
+    def params(self, slot):
+        """The six tensors of `slot` in fs_policy order, as views of the buffer."""
+        row, out, at = self.weights[int(slot)], [], 0
+        for shape in ((64, N_FEATURES), (64,), (64, 64), (64,), (N_ACTIONS, 64), (N_ACTIONS,)):
+            size = shape[0] * (shape[1] if len(shape) > 1 else 1)
+            out.append(row[at:at + size].view(shape))
+            at += size
+        return out
+
+    def push(self, actor):
+        """Copy `actor`'s weights into the next free slot, or over the oldest snapshot once the pool is full.
+        Returns the slot."""
+        slot = self.pushes % self.capacity
+        _copy_weights(self.params(slot), _checked_actor(actor))
+        self.pushes += 1
+        return slot
+
+    def assign(self, iteration, latest=0.5, seed=0):
+        """The uint8 device tensor [ceil(N / 128)] of each arena group's slot for rollout(slots=...): with
+        probability `latest` the newest snapshot, else a uniform draw over the filled slots.  A pure function
+        (pool_assignment, computed on the host) of (seed, iteration, the group's global index (arena_base +
+        128 g) / 128, filled, newest): a sharded run's assignments are the unsharded run's, cut at the shard
+        boundaries.  ValueError when the sim's arena_base is no multiple of 128 (groups would straddle shards)."""
+        torch = _torch()
+        base = int(self.sim.arena_base)
+        if base % _abi.FS_SELFPLAY_GROUP:
+            raise ValueError("OpponentPool.assign: arena_base %d is not a multiple of %d" % (base, _abi.FS_SELFPLAY_GROUP))
+        if not self.pushes:
+            raise ValueError("OpponentPool.assign: the pool is empty")
+        slots = pool_assignment(seed, iteration, base // _abi.FS_SELFPLAY_GROUP, pool_groups(self.sim.num_envs),
+                                self.filled, self.newest, latest)
+        return torch.from_numpy(slots).to(self.sim.device)
+
+    def argument(self, slots, seed, actions, logp):
+        """fs_policy_pool of this pool under `slots`, with P2's seed and sample arrays (False = off)."""
+        torch = _torch()
+        if slots is None:
+            raise ValueError("a rollout against a pool needs slots= (OpponentPool.assign)")
+        if slots.dtype != torch.uint8 or slots.device != self.weights.device or not slots.is_contiguous() or \
+                slots.numel() != pool_groups(self.sim.num_envs):
+            raise ValueError("slots must be a contiguous uint8 tensor of %d groups on %s" % (
+                pool_groups(self.sim.num_envs), self.weights.device))
+        self._slots = slots  # (kept until the next call: the launch is asynchronous)
+        return _abi.fs_policy_pool(weights=self.weights.data_ptr(), n_slots=self.capacity, slot=slots.data_ptr(),
+                                   seed=seed, actions_out=_ptr(actions), logp_out=_ptr(logp))

@@ -96,6 +96,7 @@ class FootsiesSim:
         if p1_mode not in P1_MODES:
             raise ValueError("p1_mode must be one of %s" % list(P1_MODES))
         self.num_envs = int(num_envs)
+        self.arena_base = int(arena_base)  # global index of arena 0 (a shard of a larger run)
         self.device = int(device) if self._native else torch.device("cuda", device)
         self._dev_index = int(device) if self._native else self.device.index
         self._host_mem = None

@@ -452,6 +452,34 @@ typedef struct fs_mlp {
 } fs_mlp;
 #define FS_PPO_ACTOR_PARAMS 5256  /* w1 512, b1 64, w2 4096, b2 64, w3 512, b3 8 */
 #define FS_PPO_CRITIC_PARAMS 4801 /* w1 512, b1 64, w2 4096, b2 64, w3 64, b3 1 */
+
+/* Self-play against a pool of opponents in one launch: fs_step_n_selfplay / fs_step_skip_selfplay with
+ * P2's weights chosen per group of FS_SELFPLAY_GROUP consecutive arenas (local index i, group i / 128;
+ * the last group may be partial) from `n_slots` actors held in one device buffer.  Group g plays slot
+ * min(slot[g], n_slots - 1): no value of a slot byte reads outside the pool.  Nothing else differs --
+ * P1's actor, both seeds and draw counters, the flags, traj / skip and the sample arrays are those of the
+ * call each one extends -- so arena i's results are bit for bit those of fs_step_n_selfplay (or
+ * fs_step_skip_selfplay) with p2 set to the six arrays of slot[i / 128], p2->seed = pool->seed and the same
+ * output arrays.  Split launches (n * N above the trajectory row limit) offset the sample arrays as those
+ * calls do; `slot` is per group and is read whole by every launch.
+ * Returns what the extended call returns (FS_E_UNSUPPORTED on the same handles; FS_E_INVALID for the same
+ * n, flags, max_ticks, 2^40 and int32 bounds, pool->actions_out / logp_out standing for p2's), and
+ * FS_E_INVALID for a NULL pool, weights or slot or n_slots outside 1 .. FS_SELFPLAY_POOL_MAX.
+ * (ABI 8: an addition) */
+#define FS_SELFPLAY_GROUP 128      /* arenas i with equal i / 128 share an opponent */
+#define FS_SELFPLAY_POOL_MAX 256
+typedef struct fs_policy_pool {
+  const float* weights;   /* [n_slots][FS_PPO_ACTOR_PARAMS] device, fp32, slot = w1|b1|w2|b2|w3|b3 */
+  int n_slots;            /* 1 .. FS_SELFPLAY_POOL_MAX */
+  const uint8_t* slot;    /* [ceil(N / FS_SELFPLAY_GROUP)] device: each group's slot */
+  uint64_t seed;          /* P2's sampling seed, as fs_policy.seed */
+  uint8_t* actions_out;   /* as p2->actions_out of the call it extends */
+  float* logp_out;
+} fs_policy_pool;
+int fs_step_n_selfplay_pool(fs_handle h, int n, const fs_policy* p1, const fs_policy_pool* pool, int flags,
+                            const fs_outputs* traj);
+int fs_step_skip_selfplay_pool(fs_handle h, int n, const fs_policy* p1, const fs_policy_pool* pool, int flags,
+                               int max_ticks, const fs_outputs* traj, const fs_skip_traj* skip);
 /* Device workspace fs_ppo_grad needs (independent of n). */
 size_t fs_ppo_workspace_bytes(void);
 /* One minibatch's gradient of PPO's loss, in fp32 on `stream` (a hipStream_t, NULL =
@@ -635,6 +663,10 @@ uint64_t fs_steps_taken(fs_handle h);
 /* fs_step_skip_selfplay (alone; n_steps = decisions; "fsk::selfplay::k_step_skip_selfplay<0>"): NULL on a
  * handle the call refuses */
 #define FS_KERNEL_SKIP_SELFPLAY 64
+/* fs_step_n_selfplay_pool / fs_step_skip_selfplay_pool (each alone; "fsk::selfplay::k_step_n_selfplay_pool<0>",
+ * "fsk::selfplay::k_step_skip_pool_selfplay<0>"): NULL on a handle the call refuses */
+#define FS_KERNEL_SELFPLAY_POOL 128
+#define FS_KERNEL_SKIP_SELFPLAY_POOL 256
 const char* fs_step_kernel(fs_handle h, int n_steps, int flags);
 void fs_destroy(fs_handle h);
 /* Last error message of h (or of the last failed fs_create when h is NULL). */
