@@ -48,6 +48,8 @@ FS_KERNEL_SELFPLAY = 32
 FS_KERNEL_SKIP_SELFPLAY = 64
 FS_KERNEL_SELFPLAY_POOL = 128
 FS_KERNEL_SKIP_SELFPLAY_POOL = 256
+FS_KERNEL_LEAGUE = 512
+FS_KERNEL_SKIP_LEAGUE = 1024
 FS_SELFPLAY_MIRROR = 1
 FS_SELFPLAY_GROUP = 128
 FS_SELFPLAY_POOL_MAX = 256
@@ -214,6 +216,10 @@ LIB_FUNCTIONS = {
                                           C.c_int, C.POINTER(fs_outputs)]),
     "fs_step_skip_selfplay_pool": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(fs_policy), C.POINTER(fs_policy_pool),
                                              C.c_int, C.c_int, C.POINTER(fs_outputs), C.POINTER(fs_skip_traj)]),
+    "fs_step_n_league": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(fs_policy), C.POINTER(fs_policy_pool),
+                                   C.c_int, C.POINTER(fs_outputs)]),
+    "fs_step_skip_league": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(fs_policy), C.POINTER(fs_policy_pool),
+                                      C.c_int, C.c_int, C.POINTER(fs_outputs), C.POINTER(fs_skip_traj)]),
     "fs_ppo_workspace_bytes": (C.c_size_t, []),
     "fs_ppo_eval": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.POINTER(fs_mlp), C.POINTER(fs_mlp),
                               C.c_void_p, C.c_void_p, C.c_void_p]),

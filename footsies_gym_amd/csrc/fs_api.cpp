@@ -624,15 +624,45 @@ const char* skip_unsupported(const fs_context* h) {
   return nullptr;
 }
 
-// the handles fs_step_n_selfplay / fs_step_skip_selfplay refuse
-const char* selfplay_unsupported(const fs_context* h) {
+// the handles every self-play call refuses, the league calls included
+const char* selfplay_handle_unsupported(const fs_context* h) {
   if (h->cfg.p2_mode != FS_P2_EXTERNAL)
     return "the second actor plays a remote P2: the handle needs FS_P2_EXTERNAL (this one runs the in-game bot or an "
            "idle P2)";
   if (h->cfg.p1_mode == FS_P1_BOT) return "P1 is the bot (FS_P1_BOT), not the actor";
   if (h->cfg.frame_delay > 0) return "the actors observe undelayed frames; frame_delay > 0 is not supported";
+  return nullptr;
+}
+
+// the handles fs_step_n_selfplay / fs_step_skip_selfplay and their pool forms refuse
+const char* selfplay_unsupported(const fs_context* h) {
+  if (const char* why = selfplay_handle_unsupported(h)) return why;
   if (h->p2bot_count > 0) return "some arenas' P2 is switched to the bot (fs_set_p2_mode); switch them back first";
   return nullptr;
+}
+
+// The league calls accept arenas switched to the bot group by group: the first group of FS_SELFPLAY_GROUP
+// consecutive arenas (the last may be partial) with both kinds of P2, or -1.  From the host mirror.
+int league_mixed_group(const fs_context* h) {
+  if (h->p2bot_count == 0 || h->p2bot_count == h->n) return -1;
+  for (int g = 0, i = 0; i < h->n; g++) {
+    const int end = std::min(h->n, i + FS_SELFPLAY_GROUP);
+    const uint8_t first = h->p2bot[(size_t)i];
+    for (; i < end; i++)
+      if (h->p2bot[(size_t)i] != first) return g;
+  }
+  return -1;
+}
+
+// what a league call refuses of the handle: FS_OK, or FS_E_UNSUPPORTED set on h
+int check_league(fs_handle h, const char* call) {
+  if (const char* why = selfplay_handle_unsupported(h)) return set_err(h, FS_E_UNSUPPORTED, "%s: %s", call, why);
+  const int g = league_mixed_group(h);
+  if (g >= 0)
+    return set_err(h, FS_E_UNSUPPORTED, "%s: group %d (arenas %d .. %d) has some arenas' P2 switched to the bot and "
+                   "others remote; a group of %d arenas is all bot or all remote", call, g, g * FS_SELFPLAY_GROUP,
+                   std::min(h->n, (g + 1) * FS_SELFPLAY_GROUP) - 1, FS_SELFPLAY_GROUP);
+  return FS_OK;
 }
 
 }  // namespace
@@ -842,11 +872,16 @@ fsk::PoolParams pool_params(const fs_policy_pool* pool) {
   return fsk::PoolParams{pool->weights, pool->slot, pool->n_slots};
 }
 
+// (`league`: a pool call that takes whole groups switched to the bot, fs_step_n_league / fs_step_skip_league)
 int step_n_selfplay(fs_handle h, const char* call, int n, const fs_policy* p1, const fs_policy& p2,
-                    const fsk::PoolParams* pool, int flags, const fs_outputs* traj) {
+                    const fsk::PoolParams* pool, int flags, const fs_outputs* traj, bool league = false) {
   if (n <= 0) return set_err(h, FS_E_INVALID, "%s: n must be > 0", call);
   if (flags & ~FS_SELFPLAY_MIRROR) return set_err(h, FS_E_INVALID, "%s: bad flags %d", call, flags);
-  if (const char* why = selfplay_unsupported(h)) return set_err(h, FS_E_UNSUPPORTED, "%s: %s", call, why);
+  if (league) {
+    if (int rc = check_league(h, call)) return rc;
+  } else if (const char* why = selfplay_unsupported(h)) {
+    return set_err(h, FS_E_UNSUPPORTED, "%s: %s", call, why);
+  }
   fsk::DevOutputs out;
   if (int rc = traj_outputs(h, traj, call, out)) return rc;
   if (int rc = use_device(h)) return rc;
@@ -858,7 +893,8 @@ int step_n_selfplay(fs_handle h, const char* call, int n, const fs_policy* p1, c
     q.p.pol = policy_params(p1, row);
     q.pol2 = policy_params(&p2, row);
     q.mirror = (flags & FS_SELFPLAY_MIRROR) != 0;
-    HIP_TRY(h, fsk::launch_step_selfplay(q, pool, h->cfg.float_mode, h->stream));
+    if (league) HIP_TRY(h, fsk::launch_step_league(q, *pool, h->cfg.float_mode, h->stream));
+    else HIP_TRY(h, fsk::launch_step_selfplay(q, pool, h->cfg.float_mode, h->stream));
     h->steps += (uint64_t)m;
     return (int)FS_OK;
   });
@@ -866,14 +902,18 @@ int step_n_selfplay(fs_handle h, const char* call, int n, const fs_policy* p1, c
 
 int step_skip_selfplay(fs_handle h, const char* call, int n, const fs_policy* p1, const fs_policy& p2,
                        const fsk::PoolParams* pool, int flags, int max_ticks, const fs_outputs* traj,
-                       const fs_skip_traj* skip) {
+                       const fs_skip_traj* skip, bool league = false) {
   if (n < 1) return set_err(h, FS_E_INVALID, "%s: n must be >= 1 (got %d)", call, n);
   if (int rc = check_max_ticks(h, call, max_ticks)) return rc;
   if (flags & ~FS_SELFPLAY_MIRROR) return set_err(h, FS_E_INVALID, "%s: bad flags %d", call, flags);
   // P2's draw counter is (decision index) + (tick in decision << 40): injective below 2^40 decisions
   if (h->steps + (uint64_t)n >= (1ull << 40))
     return set_err(h, FS_E_INVALID, "%s: fs_steps_taken + n must stay below 2^40", call);
-  if (const char* why = selfplay_unsupported(h)) return set_err(h, FS_E_UNSUPPORTED, "%s: %s", call, why);
+  if (league) {
+    if (int rc = check_league(h, call)) return rc;
+  } else if (const char* why = selfplay_unsupported(h)) {
+    return set_err(h, FS_E_UNSUPPORTED, "%s: %s", call, why);
+  }
   const uint64_t N = (uint64_t)h->n;
   if ((p2.actions_out || p2.logp_out) && (uint64_t)n * (uint64_t)max_ticks * N > 0x7fffffffull)
     return set_err(h, FS_E_INVALID, "%s: n * max_ticks * N = %llu entries of P2's sample arrays exceed int32", call,
@@ -891,7 +931,8 @@ int step_skip_selfplay(fs_handle h, const char* call, int n, const fs_policy* p1
     q.ticks_out = skip && skip->ticks ? skip->ticks + row_d : nullptr;
     q.capped_out = skip && skip->capped ? skip->capped + row_d : nullptr;
     q.max_ticks = max_ticks;
-    HIP_TRY(h, fsk::launch_step_skip_selfplay(q, pool, h->cfg.float_mode, h->stream));
+    if (league) HIP_TRY(h, fsk::launch_step_skip_league(q, *pool, h->cfg.float_mode, h->stream));
+    else HIP_TRY(h, fsk::launch_step_skip_selfplay(q, pool, h->cfg.float_mode, h->stream));
     h->steps += (uint64_t)m;
     return (int)FS_OK;
   });
@@ -932,6 +973,24 @@ FS_API int fs_step_skip_selfplay_pool(fs_handle h, int n, const fs_policy* p1, c
   if (int rc = check_pool(h, "fs_step_skip_selfplay_pool", pool)) return rc;
   const fsk::PoolParams pp = pool_params(pool);
   return step_skip_selfplay(h, "fs_step_skip_selfplay_pool", n, p1, pool_actor(pool), &pp, flags, max_ticks, traj, skip);
+}
+
+FS_API int fs_step_n_league(fs_handle h, int n, const fs_policy* p1, const fs_policy_pool* pool, int flags,
+                            const fs_outputs* traj) {
+  if (!h) return FS_E_INVALID;
+  if (!has_weights(p1)) return set_err(h, FS_E_INVALID, "fs_step_n_league: all six weight arrays of P1's actor required");
+  if (int rc = check_pool(h, "fs_step_n_league", pool)) return rc;
+  const fsk::PoolParams pp = pool_params(pool);
+  return step_n_selfplay(h, "fs_step_n_league", n, p1, pool_actor(pool), &pp, flags, traj, true);
+}
+
+FS_API int fs_step_skip_league(fs_handle h, int n, const fs_policy* p1, const fs_policy_pool* pool, int flags,
+                               int max_ticks, const fs_outputs* traj, const fs_skip_traj* skip) {
+  if (!h) return FS_E_INVALID;
+  if (!has_weights(p1)) return set_err(h, FS_E_INVALID, "fs_step_skip_league: all six weight arrays of P1's actor required");
+  if (int rc = check_pool(h, "fs_step_skip_league", pool)) return rc;
+  const fsk::PoolParams pp = pool_params(pool);
+  return step_skip_selfplay(h, "fs_step_skip_league", n, p1, pool_actor(pool), &pp, flags, max_ticks, traj, skip, true);
 }
 
 FS_API size_t fs_ppo_workspace_bytes(void) { return fsk::ppo_workspace_bytes(); }
@@ -1275,6 +1334,10 @@ FS_API const char* fs_step_kernel(fs_handle h, int n_steps, int flags) {
     return selfplay_unsupported(h) ? nullptr : fsk::step_selfplay_kernel_name(h->cfg.float_mode, true);
   if (h && n_steps > 0 && flags == FS_KERNEL_SKIP_SELFPLAY_POOL)
     return selfplay_unsupported(h) ? nullptr : fsk::step_skip_selfplay_kernel_name(h->cfg.float_mode, true);
+  if (h && n_steps > 0 && (flags == FS_KERNEL_LEAGUE || flags == FS_KERNEL_SKIP_LEAGUE))
+    return selfplay_handle_unsupported(h) || league_mixed_group(h) >= 0
+               ? nullptr
+               : fsk::step_league_kernel_name(h->cfg.float_mode, flags == FS_KERNEL_SKIP_LEAGUE);
   if (!h || n_steps <= 0 || (flags & ~(FS_KERNEL_HASHED | FS_KERNEL_POLICY | FS_KERNEL_PACKED))) return nullptr;
   return fsk::step_kernel_name((flags & FS_KERNEL_POLICY) != 0, (flags & FS_KERNEL_HASHED) != 0, n_steps, h->n,
                                h->cfg.float_mode, variant(h), h->geom, (flags & FS_KERNEL_PACKED) != 0,

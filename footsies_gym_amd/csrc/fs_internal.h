@@ -200,6 +200,12 @@ hipError_t launch_step_selfplay(const SelfPlayParams& q, const PoolParams* pool,
 const char* step_selfplay_kernel_name(int float_mode, bool pool);
 hipError_t launch_step_skip_selfplay(const SkipSelfPlayParams& q, const PoolParams* pool, int float_mode, hipStream_t s);
 const char* step_skip_selfplay_kernel_name(int float_mode, bool pool);
+// fs_step_n_league / fs_step_skip_league: the pool launches on a handle whose groups of FS_SELFPLAY_GROUP arenas
+// are each all remote or all switched to the bot (the caller checks); a bot group's block runs P1's actor
+// against the arena's BattleAI and ignores the pool
+hipError_t launch_step_league(const SelfPlayParams& q, const PoolParams& pool, int float_mode, hipStream_t s);
+hipError_t launch_step_skip_league(const SkipSelfPlayParams& q, const PoolParams& pool, int float_mode, hipStream_t s);
+const char* step_league_kernel_name(int float_mode, bool skip);
 hipError_t launch_reset(const ResetParams& p, int float_mode, hipStream_t s);
 hipError_t launch_set_p2(const DevState& st, int bot, const uint8_t* mask, int n, hipStream_t s);
 hipError_t launch_hash_actions(int n_envs, int n_steps, uint64_t seed, uint64_t t0, uint64_t arena_base, uint8_t* p1,

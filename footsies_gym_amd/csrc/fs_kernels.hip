@@ -2511,7 +2511,9 @@ __global__ __launch_bounds__(256) void k_step_skip(SkipParams q) {
 template <class C>
 __device__ __forceinline__ void skip_policy_body(const SkipPolicyParams& q) {
   constexpr int P2 = C::P2;
-  static_assert(C::TP == kTabLds && (P2 == FS_P2_BOT || P2 == FS_P2_NOOP), "fs_step_skip_policy: the bot or an idle P2");
+  // (kActors: a bot group of fs_step_skip_league, league::k_step_skip_league below)
+  static_assert(C::TP == kTabLds && (P2 == FS_P2_BOT || P2 == FS_P2_NOOP || P2 == kActors),
+                "fs_step_skip_policy: the bot or an idle P2");
   const StepParams& p = q.p;
   const int l = blockIdx.x * kBlock + threadIdx.x;
   const bool active = l < 2 * p.n_envs;
@@ -2521,7 +2523,7 @@ __device__ __forceinline__ void skip_policy_body(const SkipPolicyParams& q) {
   load_lane<P2>(L, p.st, a, k);
   if constexpr (C::GEOM) L.f.y = reinterpret_cast<const float*>(p.st.posy)[2 * a + (int)k];
   stage_policy(p.pol);
-  stage_tables<P2 == FS_P2_BOT>();
+  stage_tables<P2 == FS_P2_BOT || P2 == kActors>();
   if ((l & ~63) >= 2 * p.n_envs) return;  // the whole wave is past the last arena
   L.te = next_tick_entry<false>(L.f);
   const uint32_t row_step = (uint32_t)p.out_stride_steps * (uint32_t)p.n_envs;
@@ -2793,6 +2795,96 @@ __global__ __launch_bounds__(256) void k_step_skip_pool_selfplay(SkipSelfPlayPoo
   else skip_selfplay_body<TickCfg<FM, FS_P2_EXTERNAL, kPolicy>, true>(q.q, q.pool);
 }
 }  // namespace selfplay
+
+// fs_step_n_league / fs_step_skip_league: the two pool launches on a handle where whole groups of
+// FS_SELFPLAY_GROUP arenas -- a block's -- are switched to the in-game bot (fs_set_p2_mode).  Each block
+// reads its group's p2bot header bit (the host refuses a mixed group) and takes one of two bodies:
+//   remote: the pool body as it is (selfplay_body / skip_selfplay_body, POOL);
+//   bot:    P1's actor against the arena's BattleAI through the per-arena-actors tick, i.e. what
+//           k_step_n_policy<FM, kActors> / the pair loop of k_step_skip_policy run -- no P2 actor pass, the slot
+//           byte and P2's sample arrays untouched, P1's seed and counters the remote body's.
+// Per block and not per arena on two counts: the remote body stores the header with store_lane<FS_P2_EXTERNAL>,
+// which writes p2bot = 0, and the two bodies' live sets fit 256 VGPRs side by side, not merged.
+
+// The tick form's bot body: step_body's POL loop for kActors without P2 action rows (a switched arena's
+// P2 row is read and ignored there; here there is none to read).
+template <class C>
+__device__ __forceinline__ void league_bot_body(const StepParams& p) {
+  constexpr int P2 = C::P2;
+  static_assert(C::TP == kTabLds && P2 == kActors && C::KIND == kPolicy, "fs_step_n_league: a bot group");
+  const int l = blockIdx.x * kBlock + threadIdx.x;
+  const bool active = l < 2 * p.n_envs;
+  const int a = active ? l >> 1 : 0;
+  const uint32_t k = l & 1;
+  Lane L;
+  load_lane<P2>(L, p.st, a, k);
+  if constexpr (C::GEOM) L.f.y = reinterpret_cast<const float*>(p.st.posy)[2 * a + (int)k];
+  stage_policy(p.pol);
+  stage_tables<true>();
+  if ((l & ~63) >= 2 * p.n_envs) return;  // the whole wave is past the last arena
+  L.te = next_tick_entry<false>(L.f);
+  const uint32_t row_step = (uint32_t)p.out_stride_steps * (uint32_t)p.n_envs;
+  const uint32_t arena0 = (uint32_t)(l & ~63) >> 1;
+  uint32_t d0, d1;
+  policy_features(L, d0, d1);
+  const PolicyWeights W = policy_weights();
+  const uint32_t grp = prio_group();
+  uint32_t none = 0;
+  for (int t = 0; t < p.n_steps; t++) {
+    if (p.prio) prio_slice(grp);
+    const PolicyOut po = policy_act(W, d0, d1, p.pol.seed, p.arena_base + arena0, p.t0 + (uint64_t)t);
+    if (active) {
+      const uint32_t row = (uint32_t)t * (uint32_t)p.n_envs + (uint32_t)a;
+      if (k == 0) {
+        if (p.pol.actions) p.pol.actions[row] = (uint8_t)po.action;
+        if (p.pol.logp) p.pol.logp[row] = po.logp;
+      }
+      // (P2's lane: the bot's stored input plays, and its stale remote input stays as it is)
+      env_step<FS_TICK(C)>(L, k == 0 ? po.action : 0u, p, (uint32_t)t * row_step + (uint32_t)a, none);
+    }
+    policy_features(L, d0, d1);
+  }
+  if (active) {
+    store_lane<P2>(L, p.st, a);
+    if constexpr (C::GEOM) reinterpret_cast<float*>(p.st.posy)[2 * a + (int)k] = L.f.y;
+  }
+}
+
+// (a namespace of its own, as fsk::selfplay: that one holds exactly its four kernels)
+namespace league {
+// who plays P2 in this block's group: the p2bot bit of its first arena (always inside the launch)
+__device__ __forceinline__ bool bot_group(const DevState& st) {
+  static_assert(kBlock / 2 == FS_SELFPLAY_GROUP, "a group is one block's arenas");
+  const uint32_t h = (uint32_t)st.aw[blockIdx.x * (kBlock / 2)].y;
+  return __builtin_amdgcn_readfirstlane((int)((h >> kHdrP2Bot) & 1u)) != 0;
+}
+template <int FM>
+__global__ __launch_bounds__(256) void k_step_n_league(SelfPlayPoolParams q) {
+  const StepParams& p = q.q.p;
+  if (bot_group(p.st)) {
+    if (p.geom) league_bot_body<TickCfg<FM, kActors, kPolicy, kGeom>>(p);
+    else league_bot_body<TickCfg<FM, kActors, kPolicy>>(p);
+  } else {
+    if (p.geom) selfplay_body<TickCfg<FM, FS_P2_EXTERNAL, kPolicy, kGeom>, true>(q.q, q.pool);
+    else selfplay_body<TickCfg<FM, FS_P2_EXTERNAL, kPolicy>, true>(q.q, q.pool);
+  }
+}
+// The per-decision form's bot body is k_step_skip_policy's divergent pair loop on the per-arena-actors tick:
+// P1 decides once per decision and the bot acts on every tick inside env_step, so nothing needs the
+// converged wave between a decision's ticks.
+template <int FM>
+__global__ __launch_bounds__(256) void k_step_skip_league(SkipSelfPlayPoolParams q) {
+  const StepParams& p = q.q.p;
+  if (bot_group(p.st)) {
+    const SkipPolicyParams b{p, q.q.ticks_out, q.q.capped_out, q.q.max_ticks};
+    if (p.geom) skip_policy_body<TickCfg<FM, kActors, kHashed, kGeom>>(b);
+    else skip_policy_body<TickCfg<FM, kActors, kHashed>>(b);
+  } else {
+    if (p.geom) skip_selfplay_body<TickCfg<FM, FS_P2_EXTERNAL, kPolicy, kGeom>, true>(q.q, q.pool);
+    else skip_selfplay_body<TickCfg<FM, FS_P2_EXTERNAL, kPolicy>, true>(q.q, q.pool);
+  }
+}
+}  // namespace league
 
 // FootsiesEnv.reset (FE:482-515) / RESET (BC:143-146) / game start (BC:105-128), every handle
 // kind through the per-arena actor logic (off the throughput path).
@@ -3283,6 +3375,31 @@ hipError_t launch_step_skip_selfplay(const SkipSelfPlayParams& q, const PoolPara
 const char* step_skip_selfplay_kernel_name(int float_mode, bool pool) {
   static thread_local char buf[64];
   snprintf(buf, sizeof buf, "fsk::selfplay::k_step_skip_%sselfplay<%d>", pool ? "pool_" : "", float_mode == FS_FLOAT_DOUBLE);
+  return buf;
+}
+
+// fs_step_n_league / fs_step_skip_league (named after every other kernel; launched as their pool twins are)
+hipError_t launch_step_league(const SelfPlayParams& q_in, const PoolParams& pool, int float_mode, hipStream_t s) {
+  const StepParams& p = q_in.p;
+  SelfPlayPoolParams qp{q_in, pool};
+  qp.q.p.prio = launch_choice(true, false, p.n_steps, p.n_envs, FS_P2_EXTERNAL, p.geom != 0, false, p.autoreset_mode).prio;
+  const dim3 grid = grid_for(2 * p.n_envs), block(kBlock);
+  if (float_mode == FS_FLOAT_DOUBLE) hipLaunchKernelGGL(league::k_step_n_league<FS_FLOAT_DOUBLE>, grid, block, 0, s, qp);
+  else hipLaunchKernelGGL(league::k_step_n_league<FS_FLOAT_STRICT32>, grid, block, 0, s, qp);
+  return hipGetLastError();
+}
+
+hipError_t launch_step_skip_league(const SkipSelfPlayParams& q, const PoolParams& pool, int float_mode, hipStream_t s) {
+  const dim3 grid = grid_for(2 * q.p.n_envs), block(kBlock);
+  const SkipSelfPlayPoolParams qp{q, pool};
+  if (float_mode == FS_FLOAT_DOUBLE) hipLaunchKernelGGL(league::k_step_skip_league<FS_FLOAT_DOUBLE>, grid, block, 0, s, qp);
+  else hipLaunchKernelGGL(league::k_step_skip_league<FS_FLOAT_STRICT32>, grid, block, 0, s, qp);
+  return hipGetLastError();
+}
+
+const char* step_league_kernel_name(int float_mode, bool skip) {
+  static thread_local char buf[64];
+  snprintf(buf, sizeof buf, "fsk::league::k_step_%s_league<%d>", skip ? "skip" : "n", float_mode == FS_FLOAT_DOUBLE);
   return buf;
 }
 

@@ -33,8 +33,8 @@ import time
 
 from . import _abi
 from ._lib import check, lib
-from .rollout import (N_ACTIONS, N_FEATURES, FusedPolicyRollout, FusedSelfPlayRollout, OpponentPool, make_actor,
-                      obs_features)
+from .rollout import (N_ACTIONS, N_FEATURES, FusedPolicyRollout, FusedSelfPlayRollout, OpponentPool, bot_groups,
+                      make_actor, obs_features, pool_groups)
 
 
 def _torch():
@@ -369,6 +369,16 @@ class PPOTrainer:
     snapshot.  Under `group=` these three entries are rank-local.  `opponent_pool=None` is the
     single-opponent trainer, bit for bit.
 
+    `opponent_bot=f` (0 < f < 1, with either self-play mode): a league.  A fraction f of the groups of 128
+    arenas -- drawn once by rollout.bot_groups from (seed, the group's global index), so shards draw what one
+    rank over all arenas would -- plays the in-game scripted bot for the whole run, inside the same launch
+    (fs_step_n_league / fs_step_skip_league); the other groups play the pool, or the single frozen copy,
+    which is then held as a one-slot OpponentPool (so the pool entries of `stats` appear with K = 1).
+    `stats` gains `bot_episodes` and `bot_wins` (int64 scalars over the bot groups' rows of the last rollout:
+    rows with `terminated`, and those of them with reward > 0), the run's win rate against the reference's
+    yardstick; `pool_episodes` / `pool_wins` count the remote groups only.  `opponent_bot=None` is the trainer
+    without it, bit for bit.
+
     Data-parallel (`group`: a torch.distributed process group, or "default" for the default one;
     SURVEY.md §8(e)): one trainer per rank, each over its own FootsiesSim (a ShardedSim's handle:
     its arena_base keys the actor's sampling stream, so ranks roll out different arenas), all with
@@ -382,7 +392,8 @@ class PPOTrainer:
     def __init__(self, sim, actor=None, critic=None, horizon=128, gamma=0.99, lam=0.95, epochs=2, minibatches=4,
                  lr=3e-4, clip=0.2, vf_coef=0.5, ent_coef=0.01, seed=0, old_logp="behaviour", learner="hip",
                  kl_ticks=None, learner_precision="split_bf16", group=None, frame_skip=False, max_skip_ticks=64,
-                 self_play=False, opponent_refresh=1, opponent_seed=None, opponent_pool=None, opponent_latest=0.5):
+                 self_play=False, opponent_refresh=1, opponent_seed=None, opponent_pool=None, opponent_latest=0.5,
+                 opponent_bot=None):
         torch = _torch()
         decisions = isinstance(self_play, str)
         if decisions and self_play != "decisions":
@@ -406,6 +417,15 @@ class PPOTrainer:
                 raise ValueError("opponent_latest must be within [0, 1], got %r" % (opponent_latest,))
             if getattr(sim, "arena_base", 0) % _abi.FS_SELFPLAY_GROUP:
                 raise ValueError("opponent_pool needs a sim whose arena_base is a multiple of %d, got %d" % (
+                    _abi.FS_SELFPLAY_GROUP, sim.arena_base))
+        if opponent_bot is not None:
+            if not self_play:
+                raise ValueError("opponent_bot needs self_play=True or 'decisions'")
+            if not 0.0 < float(opponent_bot) < 1.0:
+                raise ValueError("opponent_bot must be a fraction of the arena groups within (0, 1) (None: no bot "
+                                 "groups), got %r" % (opponent_bot,))
+            if getattr(sim, "arena_base", 0) % _abi.FS_SELFPLAY_GROUP:
+                raise ValueError("opponent_bot needs a sim whose arena_base is a multiple of %d, got %d" % (
                     _abi.FS_SELFPLAY_GROUP, sim.arena_base))
         if old_logp not in ("behaviour", "fp32"):
             raise ValueError("old_logp must be 'behaviour' or 'fp32'")
@@ -432,10 +452,15 @@ class PPOTrainer:
         self._updates = self._opponent_taken = 0  # updates done; the count at which the opponent was copied
         self.pool, self.opponent_latest, self._pool_seed = None, float(opponent_latest), int(seed)
         self._collects = 0  # rollouts so far: the pool assignment's iteration
-        if opponent_pool is not None:  # the first snapshot: the actor as it is now
-            self.pool = OpponentPool(sim, int(opponent_pool), self.actor)
+        self.bots = None  # a league: which groups of 128 arenas play the in-game bot, fixed for the run
+        if opponent_bot is not None:
+            self.bots = bot_groups(seed, getattr(sim, "arena_base", 0) // _abi.FS_SELFPLAY_GROUP,
+                                   pool_groups(sim.num_envs), float(opponent_bot))
+        if opponent_pool is not None or self.bots is not None:  # the first snapshot: the actor as it is now
+            # (a league without opponent_pool: the single frozen copy as a one-slot pool, each push over it)
+            self.pool = OpponentPool(sim, int(opponent_pool) if opponent_pool is not None else 1, self.actor)
             self.rollout = FusedSelfPlayRollout(sim, self.actor, seed=seed, opponent_seed=opponent_seed, mirror=True,
-                                                pool=self.pool)
+                                                pool=self.pool, bots=self.bots)
         elif self.self_play:  # (opponent=None: a copy of the actor as it is now)
             self.rollout = FusedSelfPlayRollout(sim, self.actor, seed=seed, opponent_seed=opponent_seed, mirror=True)
         else:
@@ -624,6 +649,7 @@ class PPOTrainer:
         self.rollout.refresh(self.actor)
         self._updates += 1
         pool_stats = self._pool_stats(rewards, dones) if self.pool is not None else {}  # (before the push)
+        bot_stats = self._bot_stats(rewards, dones) if self.bots is not None else {}
         if self.self_play and self._updates % self.opponent_refresh == 0:  # (every rank at the same update)
             if self.pool is not None:
                 self.pool.push(self.actor)
@@ -648,6 +674,8 @@ class PPOTrainer:
             self.stats["opponent_age"] = torch.tensor(self._updates - self._opponent_taken)
         if self.pool is not None:
             self.stats.update(pool_stats, pool_filled=torch.tensor(self.pool.filled))
+        if self.bots is not None:
+            self.stats.update(bot_stats)
 
     def _pool_stats(self, rewards, dones):
         """Per slot of the pool, over the last rollout's rows (this rank's): episodes that ended and those of
@@ -656,9 +684,22 @@ class PPOTrainer:
         arena_slot = self.slots.long().repeat_interleave(_abi.FS_SELFPLAY_GROUP)[:self.sim.num_envs]
         arena_slot = arena_slot.clamp_(max=self.pool.capacity - 1)
         done = dones != 0
+        if self.bots is not None:  # (a league: the bot groups' rows belong to no slot, whatever byte they carry)
+            done = done & ~self._bot_arenas(dones.device)
         zero = torch.zeros(self.pool.capacity, dtype=torch.int64, device=dones.device)
         return {"pool_episodes": zero.index_add(0, arena_slot, done.sum(0)),
                 "pool_wins": zero.index_add(0, arena_slot, (done & (rewards > 0)).sum(0))}
+
+    def _bot_arenas(self, device):
+        """[N] bool: the arenas of the league's bot groups."""
+        torch = _torch()
+        return torch.from_numpy(self.bots).to(device).repeat_interleave(_abi.FS_SELFPLAY_GROUP)[:self.sim.num_envs]
+
+    def _bot_stats(self, rewards, dones):
+        """Over the bot groups' rows of the last rollout (this rank's): episodes that ended and those of them P1
+        won, as int64 scalars -- the win rate against the scripted bot the reference reports."""
+        done = (dones != 0) & self._bot_arenas(dones.device)
+        return {"bot_episodes": done.sum(), "bot_wins": (done & (rewards > 0)).sum()}
 
     def iterate(self):
         self.update(*self.collect())

@@ -23,7 +23,8 @@ decision and the opponent on every tick, the ones P1 skips included.
 :class:`OpponentPool` holds several opponent snapshots in one device buffer, and
 ``FusedSelfPlayRollout(sim, actor, pool=pool)`` plays them all in the same one launch
 (fs_step_n_selfplay_pool / fs_step_skip_selfplay_pool): each group of 128 consecutive arenas meets the
-snapshot its byte of ``slots`` names.
+snapshot its byte of ``slots`` names.  With ``bots=`` (a bool per group, :func:`bot_groups`) those groups play
+the in-game scripted bot instead, still in the same launch (fs_step_n_league / fs_step_skip_league).
 """
 import ctypes as C
 
@@ -272,9 +273,18 @@ class FusedSelfPlayRollout(FusedPolicyRollout):
             cls = FusedPoolSelfPlayRollout
         return super().__new__(cls)
 
-    def __init__(self, sim, actor, opponent=None, seed=0, opponent_seed=None, mirror=True, pool=None):
+    def __init__(self, sim, actor, opponent=None, seed=0, opponent_seed=None, mirror=True, pool=None, bots=None):
+        if bots is not None:  # (checked before the device is touched)
+            import numpy as np
+            if pool is None:
+                raise ValueError("FusedSelfPlayRollout: bots= needs pool= (the league calls take a pool)")
+            bots = np.asarray(bots, dtype=bool).reshape(-1)
+            if bots.size != pool_groups(sim.num_envs):
+                raise ValueError("bots must hold one bool per group: %d groups of %d arenas, got %d" % (
+                    pool_groups(sim.num_envs), _abi.FS_SELFPLAY_GROUP, bots.size))
         super().__init__(sim, actor, seed=seed)
         self.pool = pool
+        self.bots = bots
         if pool is None:
             # (cloned: the tensors may be the module's own when it already sits on the device in fp32,
             # and the opponent has to stay what it was while the learner moves on)
@@ -287,6 +297,11 @@ class FusedSelfPlayRollout(FusedPolicyRollout):
             opponent_seed = self.seed ^ 0x9E3779B97F4A7C15  # (never equal to seed)
         self.opponent_seed = int(opponent_seed) & (2**64 - 1)
         self.mirror = bool(mirror)
+        if bots is not None:
+            # a league: these groups' arenas play the in-game bot from here on (fs_step_n_league /
+            # fs_step_skip_league; the handle's P2 bit says who plays a group)
+            import numpy as np
+            sim.set_p2_mode("bot", np.repeat(bots, _abi.FS_SELFPLAY_GROUP)[:sim.num_envs])
 
     def refresh_opponent(self, actor):
         """Copy new weights into the opponent's buffers, which stay put."""
@@ -302,7 +317,8 @@ class FusedSelfPlayRollout(FusedPolicyRollout):
         form of the call and its fs_policy_pool"""
         if self.pool is None:
             return getattr(lib(), call), _policy(self.params2, self.opponent_seed, p2_actions, p2_logp)
-        return getattr(lib(), call + "_pool"), self.pool.argument(slots, self.opponent_seed, p2_actions, p2_logp)
+        name = call + "_pool" if self.bots is None else call.replace("selfplay", "league")
+        return getattr(lib(), name), self.pool.argument(slots, self.opponent_seed, p2_actions, p2_logp)
 
     def rollout(self, n, actions=None, logp=None, p2_actions=None, p2_logp=None, trajectory=None):
         """n ticks in one launch, both fighters sampled in-kernel.  `actions` / `logp` receive P1's
@@ -358,7 +374,12 @@ class FusedPoolSelfPlayRollout(FusedSelfPlayRollout):
     chosen per group of 128 consecutive arenas.  `slots` is the uint8 device tensor of each group's slot
     (OpponentPool.assign, or any [ceil(N / 128)] tensor; a value past the pool's capacity plays the last
     slot).  Every arena's results are bit for bit those of the single-opponent call with its group's
-    weights.  Everything else is FusedSelfPlayRollout's."""
+    weights.  Everything else is FusedSelfPlayRollout's.
+
+    With `bots` (a bool per group, e.g. bot_groups) the run is a league: those groups' arenas are switched to
+    the in-game bot once (sim.set_p2_mode) and both rollouts go through fs_step_n_league /
+    fs_step_skip_league -- P1's actor against the scripted BattleAI there, the pool elsewhere, in the same
+    launch.  A bot group's slot is ignored and its entries of p2_actions / p2_logp are left as they were."""
 
     def rollout(self, n, actions=None, logp=None, p2_actions=None, p2_logp=None, trajectory=None, slots=None):
         return self._rollout(slots, n, actions, logp, p2_actions, p2_logp, trajectory)
@@ -371,6 +392,22 @@ class FusedPoolSelfPlayRollout(FusedSelfPlayRollout):
 def pool_groups(num_envs):
     """Groups of FS_SELFPLAY_GROUP arenas in a handle of `num_envs` (the last may be partial)."""
     return (int(num_envs) + _abi.FS_SELFPLAY_GROUP - 1) // _abi.FS_SELFPLAY_GROUP
+
+
+def bot_groups(seed, first_group, groups, fraction):
+    """Which of `groups` consecutive arena groups from global group `first_group` on play the in-game bot, as a
+    numpy bool array, fixed for a run: group G is a bot group when mix64(seed ^ G * 0x9E3779B97F4A7C15 ^
+    0xB07 * 0xD1B54A32D192ED03) >> 40 < fraction * 2^24.  A pure function of (seed, G), counter-based like
+    pool_assignment, so a shard draws what the unsharded run draws for its groups."""
+    import numpy as np
+    if not 0.0 <= float(fraction) <= 1.0:
+        raise ValueError("fraction must be within [0, 1], got %r" % (fraction,))
+    m = 2**64 - 1
+    g = np.arange(int(first_group), int(first_group) + int(groups), dtype=np.uint64)
+    with np.errstate(over="ignore"):
+        key = np.uint64(int(seed) & m) ^ (g * np.uint64(0x9E3779B97F4A7C15))
+        v = _mix64(key ^ np.uint64((0xB07 * 0xD1B54A32D192ED03) & m)) >> np.uint64(40)
+    return v < np.uint64(int(round(float(fraction) * 2**24)))
 
 
 def _mix64(x):

@@ -480,6 +480,32 @@ int fs_step_n_selfplay_pool(fs_handle h, int n, const fs_policy* p1, const fs_po
                             const fs_outputs* traj);
 int fs_step_skip_selfplay_pool(fs_handle h, int n, const fs_policy* p1, const fs_policy_pool* pool, int flags,
                                int max_ticks, const fs_outputs* traj, const fs_skip_traj* skip);
+
+/* Self-play leagues: the two pool calls on a handle where chosen groups play the in-game bot.  The handle's
+ * P2 bit (fs_set_p2_mode) says who plays a group of FS_SELFPLAY_GROUP consecutive arenas (the last, partial
+ * one counts as a group) and may change between calls; within a group it must be uniform.
+ *   A remote group is that group of fs_step_n_selfplay_pool / fs_step_skip_selfplay_pool bit for bit: P2's
+ *     weights from slot[g], the draws
+ *       P1: u = uniform(p1->seed, cfg.arena_base + i, c), c = fs_steps_taken + k (tick or decision k),
+ *       P2: u = uniform(pool->seed, cfg.arena_base + i, c) per tick, or c + ((uint64_t)j << 40) on tick j of
+ *           a decision,
+ *     flags (0 or FS_SELFPLAY_MIRROR) and both actors' sample arrays as in those calls.
+ *   A bot group is fs_step_n_policy on such arenas: P1's actor, with the same seed, draw function and counter
+ *     c, against the arena's BattleAI, with the switch's semantics of fs_set_p2_mode (the switched-in bot is
+ *     never Reset, P2's remote input goes stale, the game RNG advances as in fs_step).  No P2 actor runs:
+ *     slot[g] is ignored and the entries of pool->actions_out / logp_out that belong to these arenas are left
+ *     untouched.  In fs_step_skip_league P1 decides once per decision and the bot acts on every tick; the
+ *     outputs are by decision as fs_step_skip_selfplay defines them (the last tick's row, the float64 reward
+ *     sum from 0.0 in tick order, skip->ticks, skip->capped).
+ * With no arena switched the calls are the pool calls bit for bit; fs_step_skip_league with max_ticks = 1 is
+ * fs_step_n_league.  Arguments, launch split and return codes are the pool calls', except that switched
+ * arenas are accepted: FS_E_UNSUPPORTED (the message names the first such group) only for a group with
+ * both kinds of P2, and as before unless the handle's P2 is FS_P2_EXTERNAL, P1 the agent and frame_delay 0.
+ * The four calls above keep refusing a handle with any arena switched.  (ABI 8: an addition) */
+int fs_step_n_league(fs_handle h, int n, const fs_policy* p1, const fs_policy_pool* pool, int flags,
+                     const fs_outputs* traj);
+int fs_step_skip_league(fs_handle h, int n, const fs_policy* p1, const fs_policy_pool* pool, int flags,
+                        int max_ticks, const fs_outputs* traj, const fs_skip_traj* skip);
 /* Device workspace fs_ppo_grad needs (independent of n). */
 size_t fs_ppo_workspace_bytes(void);
 /* One minibatch's gradient of PPO's loss, in fp32 on `stream` (a hipStream_t, NULL =
@@ -667,6 +693,10 @@ uint64_t fs_steps_taken(fs_handle h);
  * "fsk::selfplay::k_step_skip_pool_selfplay<0>"): NULL on a handle the call refuses */
 #define FS_KERNEL_SELFPLAY_POOL 128
 #define FS_KERNEL_SKIP_SELFPLAY_POOL 256
+/* fs_step_n_league / fs_step_skip_league (each alone; "fsk::league::k_step_n_league<0>",
+ * "fsk::league::k_step_skip_league<0>"): NULL on a handle the call refuses, a mixed group included */
+#define FS_KERNEL_LEAGUE 512
+#define FS_KERNEL_SKIP_LEAGUE 1024
 const char* fs_step_kernel(fs_handle h, int n_steps, int flags);
 void fs_destroy(fs_handle h);
 /* Last error message of h (or of the last failed fs_create when h is NULL). */
