@@ -237,6 +237,10 @@ LIB_FUNCTIONS = {
     "fs_ppo_features": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "fs_ppo_pack": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
                               C.c_void_p, C.c_void_p]),
+    "fs_ppo_features_p2": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p,
+                                     C.c_int64, C.c_void_p, C.c_void_p]),
+    "fs_ppo_gae_p2": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_int64,
+                                C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
     "fs_hash_actions": (C.c_int, [C.c_void_p, C.c_int, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p]),
     "fs_outputs_get": (C.c_int, [C.c_void_p, C.POINTER(fs_outputs)]),
     "fs_pack_outputs": (C.c_int, [C.c_void_p, C.c_void_p]),

@@ -1117,6 +1117,45 @@ FS_API int fs_ppo_pack(const float* x, const uint8_t* actions, const float* old_
   return FS_OK;
 }
 
+// (sel holds int32 arena indices, and one thread per selected arena is launched)
+static const char* p2_selection_error(int64_t N, const int32_t* sel, int64_t n_sel) {
+  if (N <= 0 || n_sel <= 0) return "N > 0 and n_sel > 0 required";
+  if (N > INT32_MAX || n_sel > INT32_MAX) return "N and n_sel must fit an int32";
+  if (!sel && n_sel != N) return "sel == NULL is the identity and needs n_sel == N";
+  if (reinterpret_cast<uintptr_t>(sel) % 4) return "misaligned sel";
+  return nullptr;
+}
+
+FS_API int fs_ppo_features_p2(const uint8_t* guard, const uint8_t* move, const float* move_frame,
+                              const float* position, int64_t rows, int64_t N, const int32_t* sel, int64_t n_sel,
+                              float* out, void* stream) {
+  if (!guard || !move || !move_frame || !position || !out || rows <= 0)
+    return set_err(nullptr, FS_E_INVALID, "fs_ppo_features_p2: all five arrays and rows > 0 required");
+  if (const char* why = p2_selection_error(N, sel, n_sel))
+    return set_err(nullptr, FS_E_INVALID, "fs_ppo_features_p2: %s", why);
+  if (reinterpret_cast<uintptr_t>(out) % 16 || reinterpret_cast<uintptr_t>(move_frame) % 8 ||
+      reinterpret_cast<uintptr_t>(position) % 8 || reinterpret_cast<uintptr_t>(guard) % 2 ||
+      reinterpret_cast<uintptr_t>(move) % 2)
+    return set_err(nullptr, FS_E_INVALID, "fs_ppo_features_p2: misaligned array");
+  const hipError_t e = fsk::launch_ppo_features_p2(guard, move, move_frame, position, rows, N, sel, n_sel, out,
+                                                   static_cast<hipStream_t>(stream));
+  if (e != hipSuccess) return set_err(nullptr, FS_E_DEVICE, "fs_ppo_features_p2: %s", hipGetErrorString(e));
+  return FS_OK;
+}
+
+FS_API int fs_ppo_gae_p2(const double* rewards, const uint8_t* done, const float* values, int T, int64_t N,
+                         const int32_t* sel, int64_t n_sel, float gamma, float gamma_lam, float* adv_out,
+                         float* ret_out, void* stream) {
+  if (!rewards || !done || !values || !adv_out || !ret_out || T <= 0)
+    return set_err(nullptr, FS_E_INVALID, "fs_ppo_gae_p2: all five arrays and T > 0 required");
+  if (const char* why = p2_selection_error(N, sel, n_sel))
+    return set_err(nullptr, FS_E_INVALID, "fs_ppo_gae_p2: %s", why);
+  const hipError_t e = fsk::launch_ppo_gae_p2(rewards, done, values, T, N, sel, n_sel, gamma, gamma_lam, adv_out,
+                                              ret_out, static_cast<hipStream_t>(stream));
+  if (e != hipSuccess) return set_err(nullptr, FS_E_DEVICE, "fs_ppo_gae_p2: %s", hipGetErrorString(e));
+  return FS_OK;
+}
+
 FS_API int fs_hash_actions(fs_handle h, int n_steps, uint64_t seed, uint64_t t0, uint8_t* p1_out, uint8_t* p2_out) {
   if (!h || !p1_out || n_steps <= 0) return FS_E_INVALID;
   int rc;

@@ -229,5 +229,12 @@ hipError_t launch_ppo_features(const uint8_t* guard, const uint8_t* move, const 
                                const float* position, int64_t n, float* out, hipStream_t s);
 hipError_t launch_ppo_pack(const float* x, const uint8_t* act, const float* old, const float* adv, const float* ret,
                            const float* stats, int64_t n, float* rows, hipStream_t s);
+// P2's side of a self-play trajectory over a selection of the arenas (fs_ppo_features_p2 / fs_ppo_gae_p2)
+hipError_t launch_ppo_features_p2(const uint8_t* guard, const uint8_t* move, const float* move_frame,
+                                  const float* position, int64_t rows, int64_t N, const int32_t* sel, int64_t n_sel,
+                                  float* out, hipStream_t s);
+hipError_t launch_ppo_gae_p2(const double* rew, const uint8_t* done, const float* val, int T, int64_t N,
+                             const int32_t* sel, int64_t n_sel, float gamma, float gamma_lam, float* adv, float* ret,
+                             hipStream_t s);
 
 }  // namespace fsk

@@ -887,11 +887,28 @@ __global__ __launch_bounds__(1024) void k_ppo_reduce(const float* __restrict__ p
 // load coalesced across the wave's arenas.  The TD error keeps gae()'s op order, one rounding
 // per op (r + (gamma v[t+1]) keep) - v[t]; the recursion is addcmul's fused multiply-add.
 // Rewards (f64) and done flags (u8) are read as the trajectory holds them.
-__global__ __launch_bounds__(256) void k_ppo_gae(const double* __restrict__ rew, const uint8_t* __restrict__ done,
-                                                 const float* __restrict__ val, int T, int64_t N, float gamma,
-                                                 float gamma_lam, float* __restrict__ adv, float* __restrict__ ret) {
+// P2 (k_ppo_gae_p2): the same walk for the second fighter of a zero-sum game over a selection of
+// the arenas.  Lane c of n_sel reads the rewards and done flags of arena sel[c] (c itself when sel is
+// null) out of the [T][N] trajectory, the reward negated, and its values, advantages and returns
+// are [.][n_sel] columns c.  A selected arena outside [0, N) reads nothing and gets zeros.
+template <bool P2>
+__device__ __forceinline__ void gae_body(const double* __restrict__ rew, const uint8_t* __restrict__ done,
+                                         const float* __restrict__ val, int T, int64_t N,
+                                         const int32_t* __restrict__ sel, int64_t n_sel, float gamma,
+                                         float gamma_lam, float* __restrict__ adv, float* __restrict__ ret) {
   const int64_t n = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (n >= N) return;
+  // W: the row stride of val / adv / ret, and n their column; rew / done rows are N wide, column src
+  const int64_t W = P2 ? n_sel : N;
+  if (n >= W) return;
+  int64_t src = n;
+  if constexpr (P2) {
+    if (sel) src = sel[n];
+    if (src < 0 || src >= N) {
+      for (int t = 0; t < T; ++t) adv[(int64_t)t * W + n] = ret[(int64_t)t * W + n] = 0.f;
+      return;
+    }
+  }
+  auto reward = [](double r) { return P2 ? (float)(-r) : (float)r; };
   // ticks in batches of kU, every load of a batch issued before its recursion runs (one wave per
   // SIMD at C5's 65 536 arenas: the loads in flight, not the arithmetic, set the pace); v[t + 1]
   // of tick t is the batch's previous tick's v[t], so val is read once per tick.  The T mod kU
@@ -903,34 +920,50 @@ __global__ __launch_bounds__(256) void k_ppo_gae(const double* __restrict__ rew,
     uint8_t d[kU];
     float v[kU + 1];
     double r[kU];
-    v[0] = val[(int64_t)(t + 1) * N + n];
+    v[0] = val[(int64_t)(t + 1) * W + n];
 #pragma unroll
     for (int u = 0; u < kU; ++u) {
-      const int64_t i = (int64_t)(t - u) * N + n;
-      d[u] = done[i];
+      const int64_t i = (int64_t)(t - u) * W + n;
+      const int64_t j = P2 ? (int64_t)(t - u) * N + src : i;
+      d[u] = done[j];
       v[u + 1] = val[i];
-      r[u] = rew[i];
+      r[u] = rew[j];
     }
     __builtin_amdgcn_sched_barrier(0);  // (the scheduler would sink each load to its use)
 #pragma unroll
     for (int u = 0; u < kU; ++u) {
-      const int64_t i = (int64_t)(t - u) * N + n;
+      const int64_t i = (int64_t)(t - u) * W + n;
       const float keep = 1.f - (float)d[u];
-      const float delta = ((float)r[u] + (gamma * v[u]) * keep) - v[u + 1];
+      const float delta = (reward(r[u]) + (gamma * v[u]) * keep) - v[u + 1];
       a = t - u == T - 1 ? delta : fmaf(gamma_lam * keep, a, delta);
       adv[i] = a;
       ret[i] = a + v[u + 1];
     }
   }
   for (; t >= 0; --t) {
-    const int64_t i = (int64_t)t * N + n;
-    const float keep = 1.f - (float)done[i];
+    const int64_t i = (int64_t)t * W + n;
+    const int64_t j = P2 ? (int64_t)t * N + src : i;
+    const float keep = 1.f - (float)done[j];
     const float v0 = val[i];
-    const float delta = ((float)rew[i] + (gamma * val[i + N]) * keep) - v0;
+    const float delta = (reward(rew[j]) + (gamma * val[i + W]) * keep) - v0;
     a = t == T - 1 ? delta : fmaf(gamma_lam * keep, a, delta);
     adv[i] = a;
     ret[i] = a + v0;
   }
+}
+
+__global__ __launch_bounds__(256) void k_ppo_gae(const double* __restrict__ rew, const uint8_t* __restrict__ done,
+                                                 const float* __restrict__ val, int T, int64_t N, float gamma,
+                                                 float gamma_lam, float* __restrict__ adv, float* __restrict__ ret) {
+  gae_body<false>(rew, done, val, T, N, nullptr, N, gamma, gamma_lam, adv, ret);
+}
+
+__global__ __launch_bounds__(256) void k_ppo_gae_p2(const double* __restrict__ rew, const uint8_t* __restrict__ done,
+                                                    const float* __restrict__ val, int T, int64_t N,
+                                                    const int32_t* __restrict__ sel, int64_t n_sel, float gamma,
+                                                    float gamma_lam, float* __restrict__ adv,
+                                                    float* __restrict__ ret) {
+  gae_body<true>(rew, done, val, T, N, sel, n_sel, gamma, gamma_lam, adv, ret);
 }
 
 // The update's sample table, one row per sample: x[8], action, old log-prob, the advantage
@@ -968,6 +1001,38 @@ __global__ __launch_bounds__(256) void k_ppo_features(const uint8_t* __restrict_
   o[1] = make_float4(f.x * r55, f.y * r55, p.x * r46, p.y * r46);
 }
 
+// P2's rows of the same observations (rollout.py mirror_features of obs_features), gathered: out[r][c] is
+// the row of (row r, arena sel[c]; c itself when sel is null) with each pair swapped and both positions
+// negated -- g2, g1, m2, m1, mf2, mf1, -x2, -x1 -- the products k_ppo_features', the negation a sign flip
+// (-0.0 from 0.0, as torch's negation gives).  blockIdx.y walks the rows, so a thread reads its sel
+// entry once; an arena outside [0, N) reads nothing and gets a zero row.
+__global__ __launch_bounds__(256) void k_ppo_features_p2(const uint8_t* __restrict__ guard,
+                                                         const uint8_t* __restrict__ move,
+                                                         const float* __restrict__ move_frame,
+                                                         const float* __restrict__ position, int64_t rows, int64_t N,
+                                                         const int32_t* __restrict__ sel, int64_t n_sel,
+                                                         float* __restrict__ out) {
+  const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= n_sel) return;
+  const int64_t src = sel ? (int64_t)sel[c] : c;
+  const bool ok = src >= 0 && src < N;
+  constexpr float r3 = (float)(1.0 / 3.0), r16 = (float)(1.0 / 16.0), r55 = (float)(1.0 / 55.0), r46 = (float)(1.0 / 4.6);
+  for (int64_t r = blockIdx.y; r < rows; r += gridDim.y) {
+    float4* o = reinterpret_cast<float4*>(out + (r * n_sel + c) * kF);
+    if (!ok) {
+      o[0] = o[1] = make_float4(0.f, 0.f, 0.f, 0.f);
+      continue;
+    }
+    const int64_t m = r * N + src;
+    const uchar2 g = reinterpret_cast<const uchar2*>(guard)[m];
+    const uchar2 mv = reinterpret_cast<const uchar2*>(move)[m];
+    const float2 f = reinterpret_cast<const float2*>(move_frame)[m];
+    const float2 p = reinterpret_cast<const float2*>(position)[m];
+    o[0] = make_float4((float)g.y * r3, (float)g.x * r3, (float)mv.y * r16, (float)mv.x * r16);
+    o[1] = make_float4(f.y * r55, f.x * r55, -(p.y * r46), -(p.x * r46));
+  }
+}
+
 }  // namespace fsl
 
 namespace fsk {
@@ -983,6 +1048,23 @@ hipError_t launch_ppo_gae(const double* rew, const uint8_t* done, const float* v
                           float gamma_lam, float* adv, float* ret, hipStream_t s) {
   hipLaunchKernelGGL(fsl::k_ppo_gae, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s, rew, done, val, T, N, gamma,
                      gamma_lam, adv, ret);
+  return hipGetLastError();
+}
+
+hipError_t launch_ppo_features_p2(const uint8_t* guard, const uint8_t* move, const float* move_frame,
+                                  const float* position, int64_t rows, int64_t N, const int32_t* sel, int64_t n_sel,
+                                  float* out, hipStream_t s) {
+  const unsigned gy = (unsigned)(rows < 65535 ? rows : 65535);
+  hipLaunchKernelGGL(fsl::k_ppo_features_p2, dim3((unsigned)((n_sel + 255) / 256), gy), dim3(256), 0, s, guard, move,
+                     move_frame, position, rows, N, sel, n_sel, out);
+  return hipGetLastError();
+}
+
+hipError_t launch_ppo_gae_p2(const double* rew, const uint8_t* done, const float* val, int T, int64_t N,
+                             const int32_t* sel, int64_t n_sel, float gamma, float gamma_lam, float* adv, float* ret,
+                             hipStream_t s) {
+  hipLaunchKernelGGL(fsl::k_ppo_gae_p2, dim3((unsigned)((n_sel + 255) / 256)), dim3(256), 0, s, rew, done, val, T, N,
+                     sel, n_sel, gamma, gamma_lam, adv, ret);
   return hipGetLastError();
 }
 

@@ -34,7 +34,7 @@ import time
 from . import _abi
 from ._lib import check, lib
 from .rollout import (N_ACTIONS, N_FEATURES, FusedPolicyRollout, FusedSelfPlayRollout, OpponentPool, bot_groups,
-                      make_actor, obs_features, pool_groups)
+                      make_actor, mirror_features, obs_features, pool_groups)
 
 
 def _torch():
@@ -270,42 +270,122 @@ def gae(rewards, values, dones, gamma, lam):
     return adv, adv + values[:-1]
 
 
-def gae_device(rewards, dones, values, gamma, lam):
+def _selection(sel, device, what):
+    """(pointer, count or None) of a P2 selection: a contiguous int32 vector on `device`, or None (every arena)."""
+    torch = _torch()
+    if sel is None:
+        return None, None
+    if sel.dtype != torch.int32 or sel.dim() != 1 or not sel.is_contiguous() or sel.device != device or not sel.numel():
+        raise ValueError("%s: sel must be a contiguous, non-empty int32 vector on %s (None: every arena)" % (what, device))
+    return sel.data_ptr(), sel.numel()
+
+
+def gae_device(rewards, dones, values, gamma, lam, p2=False, sel=None):
     """gae() in one launch (fs_ppo_gae): rewards [T][N] f64 and dones [T][N] u8 as the trajectory
     holds them, values [T + 1][N] f32; the TD errors in gae()'s op order, the recursion as a fused
-    multiply-add (addcmul's), so the two agree to fp32 rounding of that step."""
+    multiply-add (addcmul's), so the two agree to fp32 rounding of that step.
+
+    `p2=True` (fs_ppo_gae_p2): P2's side of a zero-sum self-play trajectory over the arenas `sel` (a
+    contiguous int32 device vector [n]; None: all N) -- the same launch on -rewards[:, sel] and
+    dones[:, sel], gathered in the kernel; values [T + 1][n], the results [T][n], bit for bit
+    gae_device on those arrays gathered first."""
     torch = _torch()
     T, N = rewards.shape
+    if sel is not None and not p2:
+        raise ValueError("gae_device: sel needs p2=True")
+    sel_ptr, n = _selection(sel, values.device, "gae_device")
+    n = N if n is None else n
     if (rewards.dtype != torch.float64 or dones.dtype != torch.uint8 or values.dtype != torch.float32
-            or tuple(dones.shape) != (T, N) or tuple(values.shape) != (T + 1, N)
+            or tuple(dones.shape) != (T, N) or tuple(values.shape) != (T + 1, n)
             or not all(t.is_contiguous() for t in (rewards, dones, values))):
-        raise ValueError("gae_device: contiguous rewards f64 [T][N], dones u8 [T][N], values f32 [T+1][N]")
-    adv = torch.empty((T, N), dtype=torch.float32, device=values.device)
+        raise ValueError("gae_device: contiguous rewards f64 [T][N], dones u8 [T][N], values f32 [T+1][N] "
+                         "(p2: [T+1][len(sel)])")
+    adv = torch.empty((T, n), dtype=torch.float32, device=values.device)
     ret = torch.empty_like(adv)
     g = torch.tensor([gamma, gamma * lam], dtype=torch.float32)  # the f32 scalars torch's ops use
     stream = torch.cuda.current_stream(values.device).cuda_stream
-    check(lib().fs_ppo_gae(C.c_void_p(rewards.data_ptr()), C.c_void_p(dones.data_ptr()), C.c_void_p(values.data_ptr()),
-                           T, N, float(g[0]), float(g[1]), C.c_void_p(adv.data_ptr()), C.c_void_p(ret.data_ptr()),
-                           C.c_void_p(stream)))
+    head = (C.c_void_p(rewards.data_ptr()), C.c_void_p(dones.data_ptr()), C.c_void_p(values.data_ptr()), T, N)
+    tail = (float(g[0]), float(g[1]), C.c_void_p(adv.data_ptr()), C.c_void_p(ret.data_ptr()), C.c_void_p(stream))
+    if p2:
+        check(lib().fs_ppo_gae_p2(*head, C.c_void_p(sel_ptr), n, *tail))
+    else:
+        check(lib().fs_ppo_gae(*head, *tail))
     return adv, ret
 
 
-def features_device(tr, out):
+def features_device(tr, out, p2=False, sel=None):
     """obs_features of every [T][N] trajectory row in one launch (fs_ppo_features) into out
     [T][N][8] f32, bit-identical to the torch ops (each division by a host scalar is torch's
-    x * f32(1 / b), the reciprocal taken in f64)."""
+    x * f32(1 / b), the reciprocal taken in f64).
+
+    `p2=True` (fs_ppo_features_p2): the rows as P2 sees them, of the arenas `sel` (a contiguous int32
+    device vector [n]; None: all N) -- out [T][n][8] = mirror_features(obs_features(...))[:, sel],
+    bit for bit; the columns of `tr` are [T][N][2] (or [N][2]: one row)."""
     torch = _torch()
     cols = (tr["guard"], tr["move"], tr["move_frame"], tr["position"])
+    if sel is not None and not p2:
+        raise ValueError("features_device: sel needs p2=True")
+    sel_ptr, n_sel = _selection(sel, out.device, "features_device")
     n = out.numel() // N_FEATURES
+    if p2:  # out rows x n_sel samples of rows x N observations
+        N = cols[0].shape[-2] if cols[0].dim() >= 2 else 0
+        rows = cols[0].numel() // (2 * N) if N else 0
+        n_sel = N if n_sel is None else n_sel
+        n, n_out = rows * N, rows * n_sel
+    else:
+        n_out = n
     if (out.dtype != torch.float32 or not out.is_contiguous() or out.shape[-1] != N_FEATURES
+            or out.numel() != n_out * N_FEATURES
             or not all(t.is_contiguous() and t.numel() == 2 * n for t in cols)
             or cols[0].dtype != torch.uint8 or cols[1].dtype != torch.uint8
             or cols[2].dtype != torch.float32 or cols[3].dtype != torch.float32):
-        raise ValueError("features_device: contiguous u8 guard / move, f32 move_frame / position [..][2], f32 out [..][8]")
+        raise ValueError("features_device: contiguous u8 guard / move, f32 move_frame / position [..][2], f32 out [..][8] "
+                         "(p2: columns [T][N][2], out [T][len(sel)][8])")
     stream = torch.cuda.current_stream(out.device).cuda_stream
-    check(lib().fs_ppo_features(*[C.c_void_p(t.data_ptr()) for t in cols], n, C.c_void_p(out.data_ptr()),
-                                C.c_void_p(stream)))
+    if p2:
+        check(lib().fs_ppo_features_p2(*[C.c_void_p(t.data_ptr()) for t in cols], rows, N, C.c_void_p(sel_ptr), n_sel,
+                                       C.c_void_p(out.data_ptr()), C.c_void_p(stream)))
+    else:
+        check(lib().fs_ppo_features(*[C.c_void_p(t.data_ptr()) for t in cols], n, C.c_void_p(out.data_ptr()),
+                                    C.c_void_p(stream)))
     return out
+
+
+def p2_eligible_groups(slots, newest, age, bots, groups=None):
+    """Which groups of 128 arenas' P2 samples a both-sides learner may use, as a numpy bool array per group:
+    exactly those whose P2 played the learner's own weights at collect time, so nothing off-policy is learnt
+    from.  `age`: updates since the opponent (a pool's newest snapshot) was copied from the learner -- above 0,
+    no group.  `slots` (uint8 per group, pool_assignment) and `newest`: a pool -- the groups whose slot is
+    `newest`; None: a single opponent -- every group.  `bots` (bool per group, bot_groups; None: no league):
+    never a bot group.  The group count is slots' or bots' length, else `groups` (default 1).  A pure host
+    function."""
+    import numpy as np
+    if slots is not None:
+        slots = np.asarray(slots).reshape(-1)
+        ok = slots == int(newest)
+    else:
+        count = groups if groups is not None else (np.asarray(bots).size if bots is not None else 1)
+        ok = np.ones(int(count), dtype=bool)
+    if bots is not None:
+        bots = np.asarray(bots, dtype=bool).reshape(-1)
+        if bots.size != ok.size:
+            raise ValueError("p2_eligible_groups: %d groups, but bots holds %d" % (ok.size, bots.size))
+        ok = ok & ~bots
+    if int(age) != 0:
+        ok = np.zeros_like(ok)
+    return ok
+
+
+def p2_selection(eligible, num_envs):
+    """The arenas of the eligible groups as a numpy int32 array, ascending (runs of 128 consecutive arenas; the
+    last group may be partial and counts with its real size), or None when every arena is selected."""
+    import numpy as np
+    eligible = np.asarray(eligible, dtype=bool).reshape(-1)
+    if eligible.size != pool_groups(num_envs):
+        raise ValueError("p2_selection: %d arenas are %d groups, got %d" % (num_envs, pool_groups(num_envs), eligible.size))
+    if eligible.all():
+        return None
+    return np.flatnonzero(np.repeat(eligible, _abi.FS_SELFPLAY_GROUP)[:int(num_envs)]).astype(np.int32)
 
 
 def pack_rows(x, actions, old, adv, ret, out=None, stats=None):
@@ -347,8 +427,25 @@ class PPOTrainer:
     as above while P2 plays a frozen, mirrored copy of the actor inside the same launch
     (FusedSelfPlayRollout, fs_step_n_selfplay; `opponent_seed` is its sampling seed).  The copy is
     re-taken from the learner after every `opponent_refresh`-th update (1: always the latest policy),
-    and `stats["opponent_age"]` holds the updates since.  P2's samples are not learnt from.
-    Data-parallel ranks hold identical weights and refresh at the same update.
+    and `stats["opponent_age"]` holds the updates since.  P2's samples are not learnt from unless
+    `both_sides=True` (below).  Data-parallel ranks hold identical weights and refresh at the same update.
+
+    `both_sides=True` (with `self_play=True`; not with "decisions", where P2 acts per tick and P1 per decision):
+    the game is treated as zero-sum and P2's samples are learnt from as well, wherever P2's weights at collect
+    time are the learner's own (p2_eligible_groups): every arena while `opponent_age` is 0 at collect (always so
+    with `opponent_refresh=1`), with a pool the groups that drew the newest snapshot while its age is 0, never a
+    league's bot group -- nothing off-policy.  P2's observation is the mirrored feature row, its action the
+    index it sampled (before swap_left_right), its old log-prob the one it sampled with, its reward P1's
+    negated, its done flag P1's `terminated`, its value the same critic's on the mirrored row; a double KO, which
+    the reference scores as a P1 win, therefore scores P2 a loss.  The rollout stores P2's samples only when a
+    group is eligible; P2's features and GAE come from fs_ppo_features_p2 / fs_ppo_gae_p2 gathered by the
+    eligible arenas, and the sample table holds P1's rows and then P2's, the advantages normalised over both.
+    Minibatches stay whole runs: of the largest power of two <= 2048 consecutive rows that tiles the table over
+    the minibatches (an update without P2 rows keeps the P1-only rule and is the P1-only update, bit for bit).
+    `stats` gains `p2_rows` (P2's samples in the last update; 0: none was eligible) and, over P2's samples of
+    the first `kl_ticks` ticks, `p2_kl_behaviour_fp32` and `p2_logp_abs_diff` (nan without P2 rows);
+    `mean_reward` and the pool and bot entries stay P1's.  Under `group=` only the single-opponent form is
+    taken (every rank then has the same row count); `both_sides=False` is the trainer without it, bit for bit.
 
     `self_play="decisions"` is both at once, the reference's FootsiesFrameSkipped over an env with a
     custom `opponent`: `horizon` counts P1's decisions as under `frame_skip=True` (capped by
@@ -393,11 +490,21 @@ class PPOTrainer:
                  lr=3e-4, clip=0.2, vf_coef=0.5, ent_coef=0.01, seed=0, old_logp="behaviour", learner="hip",
                  kl_ticks=None, learner_precision="split_bf16", group=None, frame_skip=False, max_skip_ticks=64,
                  self_play=False, opponent_refresh=1, opponent_seed=None, opponent_pool=None, opponent_latest=0.5,
-                 opponent_bot=None):
+                 opponent_bot=None, both_sides=False):
         torch = _torch()
         decisions = isinstance(self_play, str)
         if decisions and self_play != "decisions":
             raise ValueError("self_play must be False, True (per tick) or 'decisions', got %r" % (self_play,))
+        if both_sides:
+            if not self_play:
+                raise ValueError("both_sides learns from P2's samples too: it needs self_play=True")
+            if decisions:
+                raise ValueError("both_sides takes self_play=True (per tick), not 'decisions': there P1 acts once per "
+                                 "decision while P2 acts on every tick, a different decision process for each side")
+            if group is not None and (opponent_pool is not None or opponent_bot is not None):
+                raise ValueError("both_sides with opponent_pool or opponent_bot takes no group=: the P2 rows of a rank "
+                                 "depend on its own groups' draws, so the ranks' row counts -- and with them the "
+                                 "collectives they take per update -- would differ")
         if self_play and sim.p2_mode != "external":
             raise ValueError("self_play needs a sim created with p2_mode='external' (the second actor plays P2), "
                              "got %r" % (sim.p2_mode,))
@@ -483,6 +590,14 @@ class PPOTrainer:
         if self.frame_skip:  # per decision: the ticks it ran, and whether max_skip_ticks closed it
             self.ticks = torch.empty((horizon, n), dtype=torch.int32, device=dev)
             self.capped = torch.empty((horizon, n), dtype=torch.uint8, device=dev)
+        self.both_sides = bool(both_sides)
+        if self.both_sides:  # P2's samples of a rollout, stored where a group is eligible (allocated once)
+            self.p2_actions = torch.empty((horizon, n), dtype=torch.uint8, device=dev)
+            self.p2_logp = torch.empty((horizon, n), dtype=torch.float32, device=dev)
+        # the last rollout's P2 block: None (no eligible group, or both_sides off), else {"sel": the eligible
+        # arenas as an int32 device vector or None for all of them, "n": how many}
+        self._p2 = None
+        self._p2_gap = None  # prepare's fp32 log-prob gap over P2's KL samples
         self.gen = torch.Generator(device=dev)
         self.gen.manual_seed(seed)
         self.stats = {}
@@ -514,11 +629,25 @@ class PPOTrainer:
         torch = _torch()
         first = self._next_first if self._next_first is not None else obs_features(self.sim.outputs())
         pool = {}
+        slots = None
         if self.pool is not None:  # this rollout's snapshot per arena group
-            self.slots = self.pool.assign(self._collects, self.opponent_latest, self._pool_seed)
+            slots = self.pool.assignment(self._collects, self.opponent_latest, self._pool_seed)
+            self.slots = torch.from_numpy(slots).to(self.sim.device)
             pool = {"slots": self.slots}
         self._collects += 1
-        if self.frame_skip:  # a row per agent decision: its last tick, the rewards of its ticks summed
+        self._p2 = None
+        if self.both_sides:  # the groups whose P2 plays the learner's own weights in this rollout (host only)
+            ok = p2_eligible_groups(slots, self.pool.newest if self.pool is not None else None,
+                                    self._updates - self._opponent_taken, self.bots,
+                                    groups=pool_groups(self.sim.num_envs))
+            if ok.any():
+                sel = p2_selection(ok, self.sim.num_envs)
+                self._p2 = {"sel": None if sel is None else torch.from_numpy(sel).to(self.sim.device),
+                            "n": self.sim.num_envs if sel is None else int(sel.size)}
+        if self._p2 is not None:  # (per tick; with a pool or a league the same call takes the slots)
+            self.rollout.rollout(self.horizon, self.actions, self.logp, self.p2_actions, self.p2_logp,
+                                 trajectory=self.traj, **pool)
+        elif self.frame_skip:  # a row per agent decision: its last tick, the rewards of its ticks summed
             # (self_play="decisions": the same call on FusedSelfPlayRollout, P2's samples not stored)
             self.rollout.rollout_skipped(self.horizon, self.actions, self.logp, self.ticks, self.capped,
                                          trajectory=self.traj, max_ticks=self.max_skip_ticks, **pool)
@@ -550,6 +679,9 @@ class PPOTrainer:
         """The sample table of one rollout: (rows [T*N][12] -- features, action, old log-prob,
         advantage, return --, gap = behaviour log-prob - fp32 log-prob over the KL samples)."""
         torch = _torch()
+        self._p2_gap = None
+        if self._p2 is not None:  # both_sides, and the last rollout stored P2's samples of its eligible groups
+            return self._prepare_both(feats, actions, rewards, dones)
         T, N = actions.shape
         M = T * N
         nk = self.kl_ticks * N  # samples with an fp32 log-prob (all of them in "fp32" mode)
@@ -586,6 +718,61 @@ class PPOTrainer:
             gap = behav[:nk] - old32
         return rows, gap
 
+    def _prepare_both(self, feats, actions, rewards, dones):
+        """prepare() of a rollout with eligible P2 samples: one [M1 + M2][12] table, P1's M1 = T x N rows first,
+        then P2's M2 = T x n rows of the n selected arenas (tick-major like P1's), the advantages normalised
+        over all of them together.  P2's observations are the mirrored rows, its rewards P1's negated, its done
+        flags P1's, its values the same critic's on the mirrored rows; `gap` stays P1's, P2's goes to
+        ``_p2_gap``."""
+        torch = _torch()
+        T, N = actions.shape
+        sel, n = self._p2["sel"], self._p2["n"]
+        idx = None if sel is None else sel.long()
+        pick = (lambda t: t) if idx is None else (lambda t: t.index_select(1, idx))
+        with torch.no_grad():
+            feats2 = torch.empty((T + 1, n, N_FEATURES), dtype=torch.float32, device=feats.device)
+            first2 = mirror_features(feats[0])
+            feats2[0] = first2 if idx is None else first2.index_select(0, idx)
+            if self._grad is not None:
+                features_device(self.traj, feats2[1:], p2=True, sel=sel)
+            else:
+                feats2[1:] = pick(mirror_features(feats[1:]))
+            sides = []  # per side: (x, actions, old log-probs, advantages, returns, gap), flat over its rows
+            for f, a, behav, w in ((feats, actions.reshape(-1), self.logp.reshape(-1), N),
+                                   (feats2, pick(self.p2_actions).reshape(-1), pick(self.p2_logp).reshape(-1), n)):
+                p2 = f is feats2
+                M, nk = T * w, self.kl_ticks * w
+                x = f[:T].reshape(M, N_FEATURES)
+                if self._grad is not None:  # (the same calls as prepare's, per side)
+                    if nk == M and self._grad.precision == "fp32":
+                        v, old32 = self._grad.evaluate(f.view(-1, N_FEATURES), a, nk)
+                    else:
+                        v, _ = self._grad.evaluate(f.view(-1, N_FEATURES))
+                        _, old32 = self._grad.evaluate(x[:nk].contiguous(), a, nk, precision="fp32", values=False)
+                    adv, ret = gae_device(rewards, dones, v.view(T + 1, w), self.gamma, self.lam, p2=p2,
+                                          sel=sel if p2 else None)
+                else:
+                    v = self.critic(f).squeeze(-1)
+                    old32 = torch.log_softmax(self.actor(x[:nk]), dim=1).gather(1, a[:nk, None].long())[:, 0]
+                    r, d = (pick(-rewards), pick(dones)) if p2 else (rewards, dones)
+                    adv, ret = gae(r.float(), v, d.float(), self.gamma, self.lam)
+                old = behav if self.old_logp == "behaviour" else old32
+                sides.append((x, a, old, adv.reshape(M), ret.reshape(M), behav[:nk] - old32))
+            adv_all = torch.cat([sides[0][3], sides[1][3]])
+            st = self._adv_stats(adv_all)
+            if st is None:
+                st = torch.stack([adv_all.mean(), adv_all.std()])
+            M1 = T * N
+            if self._grad is not None:  # each side packed into its part of the table, with the joint statistics
+                rows = torch.empty((M1 + T * n, 12), dtype=torch.float32, device=feats.device)
+                for (x, a, old, adv, ret, _), out in zip(sides, (rows[:M1], rows[M1:])):
+                    pack_rows(x, a, old, adv, ret, out=out, stats=st)
+            else:
+                rows = torch.cat([torch.cat([x, a[:, None].float(), old[:, None], ((adv - st[0]) / (st[1] + 1e-8))[:, None],
+                                             ret[:, None]], dim=1) for x, a, old, adv, ret, _ in sides])
+            self._p2_gap = sides[1][5]
+        return rows, sides[0][5]
+
     def _adv_stats(self, adv):
         """The advantage normalisation's (mean, std) over every rank (data-parallel), else None
         (this rank's own, as pack_rows / the torch learner compute them)."""
@@ -620,6 +807,12 @@ class PPOTrainer:
         # that many consecutive arenas) when they tile the batch, so each minibatch is gathered as
         # whole runs (row copies) instead of 2 M scattered rows; per-sample otherwise.
         C = _SHUFFLE_CHUNK if M % (_SHUFFLE_CHUNK * self.minibatches) == 0 else 1
+        if rows.shape[0] != M:  # both_sides with P2 rows: the largest power-of-two run that tiles this table
+            # (a table without P2 rows keeps the rule above, so that update is the P1-only trainer's, bit for bit)
+            M = rows.shape[0]
+            C = _SHUFFLE_CHUNK
+            while C > 1 and M % (C * self.minibatches):
+                C //= 2
         runs = rows.view(M // C, C, rows.shape[1])
         nb = (M // C + self.minibatches - 1) // self.minibatches
         for _ in range(self.epochs):
@@ -672,6 +865,10 @@ class PPOTrainer:
             self.stats["capped"] = self.capped.sum()
         if self.self_play:  # updates since the opponent's weights were copied from the learner
             self.stats["opponent_age"] = torch.tensor(self._updates - self._opponent_taken)
+        if self.both_sides:  # P2's samples in this update (0: no group was eligible; its two diagnostics are then nan)
+            p2_gap = self._p2_gap if self._p2_gap is not None else torch.full((1,), float("nan"), device=rows.device)
+            self.stats.update(p2_rows=torch.tensor(rows.shape[0] - T * N), p2_kl_behaviour_fp32=p2_gap.mean(),
+                              p2_logp_abs_diff=p2_gap.abs().mean())
         if self.pool is not None:
             self.stats.update(pool_stats, pool_filled=torch.tensor(self.pool.filled))
         if self.bots is not None:
@@ -717,4 +914,5 @@ class PPOTrainer:
         return iterations * self.horizon * self.sim.num_envs / (time.perf_counter() - t0)
 
 
-__all__ = ["PPOTrainer", "PPOGrad", "make_critic", "gae", "gae_device", "pack_rows", "features_device", "N_ACTIONS"]
+__all__ = ["PPOTrainer", "PPOGrad", "make_critic", "gae", "gae_device", "pack_rows", "features_device",
+           "p2_eligible_groups", "p2_selection", "N_ACTIONS"]

@@ -492,15 +492,17 @@ class OpponentPool:
         (pool_assignment, computed on the host) of (seed, iteration, the group's global index (arena_base +
         128 g) / 128, filled, newest): a sharded run's assignments are the unsharded run's, cut at the shard
         boundaries.  ValueError when the sim's arena_base is no multiple of 128 (groups would straddle shards)."""
-        torch = _torch()
+        return _torch().from_numpy(self.assignment(iteration, latest, seed)).to(self.sim.device)
+
+    def assignment(self, iteration, latest=0.5, seed=0):
+        """assign()'s slots as the numpy uint8 array they are drawn as on the host."""
         base = int(self.sim.arena_base)
         if base % _abi.FS_SELFPLAY_GROUP:
             raise ValueError("OpponentPool.assign: arena_base %d is not a multiple of %d" % (base, _abi.FS_SELFPLAY_GROUP))
         if not self.pushes:
             raise ValueError("OpponentPool.assign: the pool is empty")
-        slots = pool_assignment(seed, iteration, base // _abi.FS_SELFPLAY_GROUP, pool_groups(self.sim.num_envs),
-                                self.filled, self.newest, latest)
-        return torch.from_numpy(slots).to(self.sim.device)
+        return pool_assignment(seed, iteration, base // _abi.FS_SELFPLAY_GROUP, pool_groups(self.sim.num_envs),
+                               self.filled, self.newest, latest)
 
     def argument(self, slots, seed, actions, logp):
         """fs_policy_pool of this pool under `slots`, with P2's seed and sample arrays (False = off)."""

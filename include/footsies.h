@@ -574,6 +574,32 @@ int fs_ppo_features(const uint8_t* guard, const uint8_t* move, const float* move
  * old, (adv - mean) / (std + 1e-8), ret. */
 int fs_ppo_pack(const float* x, const uint8_t* actions, const float* old_logp, const float* adv, const float* ret,
                 const float* stats, int64_t n, float* rows_out, void* stream);
+/* P2's side of a mirrored self-play trajectory (fs_step_n_selfplay and its pool / league forms under
+ * FS_SELFPLAY_MIRROR), for a learner that uses both fighters' samples; asynchronously on `stream`.  (Additions
+ * within ABI 8: no existing struct or call changed.)
+ *   P2's observation before tick t is the mirror of P1's feature row: each pair swapped and both positions
+ * negated, g2, g1, m2, m1, mf2, mf1, -x2, -x1 -- what the in-kernel P2 actor sees.  Its action is its sampled
+ * index as fs_policy.actions_out holds it (before Left and Right are exchanged for the game), its old
+ * log-probability fs_policy.logp_out.  Its reward is P1's negated: the game is treated as zero-sum, which is
+ * exact in f64 for the dense and the sparse reward alike (the dense terms and the terminal correction +-1 - cum
+ * negate exactly).  It is FootsiesEnv's reward seen from P2's chair except on a double KO, which FootsiesEnv
+ * scores as a P1 win (p2Vital == 0): P2 is then scored a loss, not a win; the outputs carry no vitals, so the
+ * two cannot be told apart here.  Its done flag is P1's `terminated`.
+ *   `sel`: device int32 [n_sel], the arenas whose P2 samples are wanted, in any order, repeats allowed (runs of
+ * consecutive arenas keep the loads coalesced); NULL is the identity 0 .. N - 1 and needs n_sel == N.  The
+ * entries are device data and are not checked on the host: one outside [0, N) reads nothing, and its outputs
+ * are zeros.
+ *   fs_ppo_features_p2: guard, move, move_frame, position are [rows][N][2] trajectory columns; out device
+ * [rows][n_sel][8] f32 (16-byte aligned), out[r][c] = the mirrored row of fs_ppo_features' row of (r, sel[c]),
+ * bit for bit rollout.py's mirror_features(obs_features(...)) (the negation a sign flip: -0.0 from 0.0).
+ *   fs_ppo_gae_p2: fs_ppo_gae on the rewards negated and the rewards and done flags ([T][N]) gathered by sel;
+ * values device [T + 1][n_sel] f32, adv_out and ret_out [T][n_sel] f32; bit for bit fs_ppo_gae on those
+ * arrays gathered first. */
+int fs_ppo_features_p2(const uint8_t* guard, const uint8_t* move, const float* move_frame, const float* position,
+                       int64_t rows, int64_t N, const int32_t* sel, int64_t n_sel, float* out, void* stream);
+int fs_ppo_gae_p2(const double* rewards, const uint8_t* done, const float* values, int T, int64_t N,
+                  const int32_t* sel, int64_t n_sel, float gamma, float gamma_lam,
+                  float* adv_out, float* ret_out, void* stream);
 
 /* Fill device arrays p1_out/p2_out [n_steps][N] with the synthetic action stream
  * of fs_step_n (splitmix64 hash of (seed, arena_base + i, t0 + k, player)),
