@@ -12,6 +12,8 @@
 // fragments are built in that order).  tanh's scale and offset are folded into the weights (see
 // kTanhScale), so a hidden value costs v_exp_f32 + v_add + v_rcp_f32 + half a v_cvt_pk_bf16_f32.
 // Weights, inputs and the hidden r values are bf16; accumulation is f32.
+// The draw never returns an action whose softmax weight is exactly 0 (finite logits): see the
+// selection in policy_act_side; tests/sampler_ref.py restates it bit for bit.
 //
 // MFMA operand maps (gfx950, 32x32x16 bf16): lane l, r = l & 31, h = l >> 5 holds
 // A[row r][k = 8h + j] and B[k = 8h + j][col r] in element j; C/D: col = r,
@@ -250,10 +252,16 @@ __device__ __forceinline__ PolicyOut policy_act_side(const WS& W, uint32_t d0, u
   if constexpr (ARENA_T)
     tr = (uint64_t)lane_read((uint32_t)t, 2 * r) | ((uint64_t)lane_read((uint32_t)(t >> 32), 2 * r) << 32);
   const float target = policy_uniform(seed, arena0 + (uint64_t)r, tr) * total;
-  // first action whose cumulative weight exceeds the target (half h = 0 starts at 0, h = 1 at s_lo)
+  // first action whose cumulative weight exceeds the target (half h = 0 starts at 0, h = 1 at s_lo).
+  // Past c2 the half's pick is its last action of non-zero weight, not blindly its fourth: the upper
+  // half's thresholds (s_lo + e4) + e5 ... and total = s_lo + s_hi associate differently, so c2 can
+  // round below total where e7 == 0, and a uniform in its top values would then draw an action of
+  // probability zero.  A zero weight inside a half adds nothing to its threshold (c_k == c_k-1), so
+  // with this no action of zero weight is ever returned.
   const float base = h == 0 ? 0.0f : s_lo;
   const float c0 = base + e0, c1 = c0 + e1, c2 = c1 + e2;
-  const uint32_t i_mine = target < c0 ? 0u : target < c1 ? 1u : target < c2 ? 2u : 3u;
+  const uint32_t i_last = e3 > 0.0f ? 3u : e2 > 0.0f ? 2u : e1 > 0.0f ? 1u : 0u;
+  const uint32_t i_mine = target < c0 ? 0u : target < c1 ? 1u : target < c2 ? 2u : i_last;
   const uint32_t i_other = lane_read(i_mine, l ^ 32);
   const bool low = target < s_lo;
   const uint32_t action = low ? (h == 0 ? i_mine : i_other) : 4u + (h == 0 ? i_other : i_mine);

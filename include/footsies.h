@@ -342,7 +342,9 @@ int fs_step_n_packed(fs_handle h, int n, const uint8_t* p1_act, const uint8_t* p
  * P1 then P2 (footsies_gym_amd/rollout.py obs_features), fp32 device weights in
  * torch nn.Linear layouts (weight [out][in]), computed in bf16 with f32
  * accumulation.  The action is drawn from softmax(logits) by inverse CDF with
- * u = uniform(seed, env, t) (fs_policy.h policy_uniform), t = fs_steps_taken + k. */
+ * u = uniform(seed, env, t) (fs_policy.h policy_uniform), t = fs_steps_taken + k.
+ * For finite logits the draw is never an action whose softmax weight underflowed
+ * to exactly zero in float32 (a logit more than ~87 below the largest). */
 typedef struct fs_policy {
   const float* w1; /* [64][8] */
   const float* b1; /* [64] */

@@ -79,7 +79,9 @@ def logits(params, feats):
 def sample(lg, u):
     """Inverse-CDF draw per row of logits `lg` [N, 8] with uniforms `u` [N]; returns
     (action, logp, margin): margin is how far (in probability) u sits from the nearest CDF
-    boundary, below which rounding may legitimately pick the neighbouring action."""
+    boundary, below which rounding may legitimately pick the neighbouring action.  The band that
+    margin excludes, and the final boundary cdf = 1 that it does not look at, are covered by the
+    exact restatement of the selection (tests/sampler_ref.py, tests/test_gpu_sampler_exact.py)."""
     z = lg.astype(np.float64) - lg.max(axis=1, keepdims=True)
     p = np.exp(z)
     p /= p.sum(axis=1, keepdims=True)

@@ -6,7 +6,10 @@ arenas).  The actor matches its host restatement (tests/policy_ref.py): the same
 wherever the uniform is not within rounding distance of a CDF boundary, and log-probabilities
 within 0.05 (bf16 inputs, weights and hidden activations; f32 accumulation).  And it matches the
 fp32 torch actor that ppo.py trains within the bf16 tolerances stated at _check_fp32 (measured
-at 65 536 x 64: KL estimate 1.5e-5 per tick, mean |d logp| 3e-3, max 0.052)."""
+at 65 536 x 64: KL estimate 1.5e-5 per tick, mean |d logp| 3e-3, max 0.052).
+
+The draws these margins leave out (the band around every CDF boundary, and the final boundary
+cdf = 1, which no margin looks at) are held exactly by tests/test_gpu_sampler_exact.py."""
 import numpy as np
 import pytest
 
