@@ -11,6 +11,7 @@
 #include <unistd.h>
 
 #include <algorithm>
+#include <cerrno>
 #include <cmath>
 #include <condition_variable>
 #include <cstdarg>
@@ -265,6 +266,12 @@ FS_API int fs_create(const fs_config* cfg, fs_handle* out) {
   h->cfg = *cfg;
   h->n = cfg->num_envs;
   h->device = cfg->device_id;
+  if (const char* e = getenv("FOOTSIES_STEPS_START")) {  // test hook: fs_steps_taken starts here (uint64, decimal or 0x hex)
+    char* end = nullptr;
+    errno = 0;
+    const unsigned long long v = strtoull(e, &end, 0);
+    if (errno == 0 && end != e && *end == '\0' && *e != '-') h->steps = (uint64_t)v;  // (else ignored)
+  }
   const size_t N = (size_t)h->n;
   int rc = FS_OK;
   auto fail = [&](int code) {

@@ -700,6 +700,8 @@ void* fs_stream(fs_handle h);
 #define FS_STREAM_OWN ((void*)(intptr_t)-1)
 int fs_set_stream(fs_handle h, void* stream);
 int fs_num_envs(fs_handle h);
+/* Steps (ticks, or decisions of the skip calls) taken so far: the counter of every in-kernel draw.  0 at
+ * fs_create, unless the test hook FOOTSIES_STEPS_START (a uint64, decimal or 0x hex) starts it elsewhere. */
 uint64_t fs_steps_taken(fs_handle h);
 /* The kernel a step call on h would launch, as rocprofv3 names it ("fsk::k_step_n<0, 0>"):
  * n_steps = 1 is fs_step / fs_step_masked, n_steps > 1 fs_step_n with action rows (its launches

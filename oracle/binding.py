@@ -52,12 +52,13 @@ def lib():
     return _lib
 
 
-def hash_actions(seed, n_envs, t, player):
-    """Vectorised splitmix64 action stream, numpy-side."""
-    M = np.uint64(0xFFFFFFFFFFFFFFFF)
-    env = np.arange(n_envs, dtype=np.uint64)
+def hash_actions(seed, n_envs, t, player, env0=0):
+    """Vectorised splitmix64 action stream, numpy-side: arenas env0 .. env0 + n_envs - 1
+    (global indices: env0 is the handle's arena_base) at tick t, all uint64 and wrapping as in the kernels."""
+    M = 0xFFFFFFFFFFFFFFFF
+    env = np.uint64(int(env0) & M) + np.arange(n_envs, dtype=np.uint64)
     with np.errstate(over="ignore"):
-        x = np.uint64(seed) ^ (env * np.uint64(0x9E3779B97F4A7C15)) ^ np.uint64((t << 1) | player)
+        x = np.uint64(int(seed) & M) ^ (env * np.uint64(0x9E3779B97F4A7C15)) ^ np.uint64(((int(t) << 1) | player) & M)
         x = x + np.uint64(0x9E3779B97F4A7C15)
         x = (x ^ (x >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
         x = (x ^ (x >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)

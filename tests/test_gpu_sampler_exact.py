@@ -189,12 +189,12 @@ def _opponents(sim, form, i, actor1, mirror):
     return ro, tuple(_live2(i, k) for k in SLOT_OF_GROUP), ((1,) if bots else ()), dict(slots=slots)
 
 
-def _check_p2(fig, what, lives2, bot_groups, seed, counter, a2, lp2, written=None):
+def _check_p2(fig, what, lives2, bot_groups, seed, counter, a2, lp2, written=None, arena=ARENA):
     for g, sl in enumerate(GROUPS):
         w = None if written is None else written[..., sl]
         if g in bot_groups:  # the bot plays here: nothing of P2's arrays is written
             w = np.zeros(a2[..., sl].shape, dtype=bool)
-        check(fig, "%s, P2 group %d" % (what, g), lives2[g], seed, counter, a2[..., sl], lp2[..., sl], w, ARENA[sl])
+        check(fig, "%s, P2 group %d" % (what, g), lives2[g], seed, counter, a2[..., sl], lp2[..., sl], w, arena[sl])
 
 
 @pytest.mark.parametrize("mirror", [False, True])

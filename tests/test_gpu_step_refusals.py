@@ -6,7 +6,7 @@ share shows up here as a changed message, not only as a changed code.  Each refu
 before a kernel launch (most before the device is touched at all), so no case runs a kernel with a
 bad argument.  After its refusals every handle takes one accepted call: nothing was left behind.
 
-The 2^40 counter refusal of fs_step_skip_selfplay is not covered: nothing sets fs_steps_taken.
+(The 2^40 counter refusal of the per-decision self-play calls: tests/test_gpu_wide_counters.py.)
 """
 import ctypes as C
 
