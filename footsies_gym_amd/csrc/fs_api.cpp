@@ -661,10 +661,11 @@ int league_mixed_group(const fs_context* h) {
   return -1;
 }
 
-// what a league call refuses of the handle: FS_OK, or FS_E_UNSUPPORTED set on h
-int check_league(fs_handle h, const char* call) {
-  if (const char* why = selfplay_handle_unsupported(h)) return set_err(h, FS_E_UNSUPPORTED, "%s: %s", call, why);
-  const int g = league_mixed_group(h);
+// what a self-play call (`league`: a league call) refuses of the handle: FS_OK, or FS_E_UNSUPPORTED set on h
+int check_selfplay_handle(fs_handle h, const char* call, bool league) {
+  if (const char* why = league ? selfplay_handle_unsupported(h) : selfplay_unsupported(h))
+    return set_err(h, FS_E_UNSUPPORTED, "%s: %s", call, why);
+  const int g = league ? league_mixed_group(h) : -1;
   if (g >= 0)
     return set_err(h, FS_E_UNSUPPORTED, "%s: group %d (arenas %d .. %d) has some arenas' P2 switched to the bot and "
                    "others remote; a group of %d arenas is all bot or all remote", call, g, g * FS_SELFPLAY_GROUP,
@@ -856,27 +857,25 @@ FS_API int fs_step_skip_policy(fs_handle h, int n, const fs_policy* pol, int max
 
 namespace {
 
-// a pool argument in full: FS_OK, or the refusal set on h
-int check_pool(fs_handle h, const char* call, const fs_policy_pool* pool) {
+// The actor arguments of a pool or league entry point: FS_OK with the pool as the kernels take it (`pp`) and
+// P2's seed and sample arrays as the fs_policy the shared code reads (`p2`: no weights, the kernel takes
+// them from the pool), or the refusal set on h.
+struct PoolCall {
+  fsk::PoolParams pp;
+  fs_policy p2;
+};
+int pool_call(fs_handle h, const char* call, const fs_policy* p1, const fs_policy_pool* pool, PoolCall& c) {
+  if (!has_weights(p1)) return set_err(h, FS_E_INVALID, "%s: all six weight arrays of P1's actor required", call);
   if (!pool || !pool->weights || !pool->slot)
     return set_err(h, FS_E_INVALID, "%s: the pool, its weights and its slot array are required", call);
   if (pool->n_slots < 1 || pool->n_slots > FS_SELFPLAY_POOL_MAX)
     return set_err(h, FS_E_INVALID, "%s: n_slots must be 1 .. %d (got %d)", call, FS_SELFPLAY_POOL_MAX, pool->n_slots);
+  c.pp = fsk::PoolParams{pool->weights, pool->slot, pool->n_slots};
+  c.p2 = fs_policy{};
+  c.p2.seed = pool->seed;
+  c.p2.actions_out = pool->actions_out;
+  c.p2.logp_out = pool->logp_out;
   return FS_OK;
-}
-
-// P2's seed and sample arrays of a pool call as the fs_policy the shared code reads (no weights: the
-// kernel takes them from the pool)
-fs_policy pool_actor(const fs_policy_pool* pool) {
-  fs_policy p{};
-  p.seed = pool->seed;
-  p.actions_out = pool->actions_out;
-  p.logp_out = pool->logp_out;
-  return p;
-}
-
-fsk::PoolParams pool_params(const fs_policy_pool* pool) {
-  return fsk::PoolParams{pool->weights, pool->slot, pool->n_slots};
 }
 
 // (`league`: a pool call that takes whole groups switched to the bot, fs_step_n_league / fs_step_skip_league)
@@ -884,11 +883,7 @@ int step_n_selfplay(fs_handle h, const char* call, int n, const fs_policy* p1, c
                     const fsk::PoolParams* pool, int flags, const fs_outputs* traj, bool league = false) {
   if (n <= 0) return set_err(h, FS_E_INVALID, "%s: n must be > 0", call);
   if (flags & ~FS_SELFPLAY_MIRROR) return set_err(h, FS_E_INVALID, "%s: bad flags %d", call, flags);
-  if (league) {
-    if (int rc = check_league(h, call)) return rc;
-  } else if (const char* why = selfplay_unsupported(h)) {
-    return set_err(h, FS_E_UNSUPPORTED, "%s: %s", call, why);
-  }
+  if (int rc = check_selfplay_handle(h, call, league)) return rc;
   fsk::DevOutputs out;
   if (int rc = traj_outputs(h, traj, call, out)) return rc;
   if (int rc = use_device(h)) return rc;
@@ -916,11 +911,7 @@ int step_skip_selfplay(fs_handle h, const char* call, int n, const fs_policy* p1
   // P2's draw counter is (decision index) + (tick in decision << 40): injective below 2^40 decisions
   if (h->steps + (uint64_t)n >= (1ull << 40))
     return set_err(h, FS_E_INVALID, "%s: fs_steps_taken + n must stay below 2^40", call);
-  if (league) {
-    if (int rc = check_league(h, call)) return rc;
-  } else if (const char* why = selfplay_unsupported(h)) {
-    return set_err(h, FS_E_UNSUPPORTED, "%s: %s", call, why);
-  }
+  if (int rc = check_selfplay_handle(h, call, league)) return rc;
   const uint64_t N = (uint64_t)h->n;
   if ((p2.actions_out || p2.logp_out) && (uint64_t)n * (uint64_t)max_ticks * N > 0x7fffffffull)
     return set_err(h, FS_E_INVALID, "%s: n * max_ticks * N = %llu entries of P2's sample arrays exceed int32", call,
@@ -958,10 +949,9 @@ FS_API int fs_step_n_selfplay(fs_handle h, int n, const fs_policy* p1, const fs_
 FS_API int fs_step_n_selfplay_pool(fs_handle h, int n, const fs_policy* p1, const fs_policy_pool* pool, int flags,
                                    const fs_outputs* traj) {
   if (!h) return FS_E_INVALID;
-  if (!has_weights(p1)) return set_err(h, FS_E_INVALID, "fs_step_n_selfplay_pool: all six weight arrays of P1's actor required");
-  if (int rc = check_pool(h, "fs_step_n_selfplay_pool", pool)) return rc;
-  const fsk::PoolParams pp = pool_params(pool);
-  return step_n_selfplay(h, "fs_step_n_selfplay_pool", n, p1, pool_actor(pool), &pp, flags, traj);
+  PoolCall c;
+  if (int rc = pool_call(h, "fs_step_n_selfplay_pool", p1, pool, c)) return rc;
+  return step_n_selfplay(h, "fs_step_n_selfplay_pool", n, p1, c.p2, &c.pp, flags, traj);
 }
 
 FS_API int fs_step_skip_selfplay(fs_handle h, int n, const fs_policy* p1, const fs_policy* p2, int flags,
@@ -975,29 +965,25 @@ FS_API int fs_step_skip_selfplay(fs_handle h, int n, const fs_policy* p1, const 
 FS_API int fs_step_skip_selfplay_pool(fs_handle h, int n, const fs_policy* p1, const fs_policy_pool* pool, int flags,
                                       int max_ticks, const fs_outputs* traj, const fs_skip_traj* skip) {
   if (!h) return FS_E_INVALID;
-  if (!has_weights(p1))
-    return set_err(h, FS_E_INVALID, "fs_step_skip_selfplay_pool: all six weight arrays of P1's actor required");
-  if (int rc = check_pool(h, "fs_step_skip_selfplay_pool", pool)) return rc;
-  const fsk::PoolParams pp = pool_params(pool);
-  return step_skip_selfplay(h, "fs_step_skip_selfplay_pool", n, p1, pool_actor(pool), &pp, flags, max_ticks, traj, skip);
+  PoolCall c;
+  if (int rc = pool_call(h, "fs_step_skip_selfplay_pool", p1, pool, c)) return rc;
+  return step_skip_selfplay(h, "fs_step_skip_selfplay_pool", n, p1, c.p2, &c.pp, flags, max_ticks, traj, skip);
 }
 
 FS_API int fs_step_n_league(fs_handle h, int n, const fs_policy* p1, const fs_policy_pool* pool, int flags,
                             const fs_outputs* traj) {
   if (!h) return FS_E_INVALID;
-  if (!has_weights(p1)) return set_err(h, FS_E_INVALID, "fs_step_n_league: all six weight arrays of P1's actor required");
-  if (int rc = check_pool(h, "fs_step_n_league", pool)) return rc;
-  const fsk::PoolParams pp = pool_params(pool);
-  return step_n_selfplay(h, "fs_step_n_league", n, p1, pool_actor(pool), &pp, flags, traj, true);
+  PoolCall c;
+  if (int rc = pool_call(h, "fs_step_n_league", p1, pool, c)) return rc;
+  return step_n_selfplay(h, "fs_step_n_league", n, p1, c.p2, &c.pp, flags, traj, true);
 }
 
 FS_API int fs_step_skip_league(fs_handle h, int n, const fs_policy* p1, const fs_policy_pool* pool, int flags,
                                int max_ticks, const fs_outputs* traj, const fs_skip_traj* skip) {
   if (!h) return FS_E_INVALID;
-  if (!has_weights(p1)) return set_err(h, FS_E_INVALID, "fs_step_skip_league: all six weight arrays of P1's actor required");
-  if (int rc = check_pool(h, "fs_step_skip_league", pool)) return rc;
-  const fsk::PoolParams pp = pool_params(pool);
-  return step_skip_selfplay(h, "fs_step_skip_league", n, p1, pool_actor(pool), &pp, flags, max_ticks, traj, skip, true);
+  PoolCall c;
+  if (int rc = pool_call(h, "fs_step_skip_league", p1, pool, c)) return rc;
+  return step_skip_selfplay(h, "fs_step_skip_league", n, p1, c.p2, &c.pp, flags, max_ticks, traj, skip, true);
 }
 
 FS_API size_t fs_ppo_workspace_bytes(void) { return fsk::ppo_workspace_bytes(); }

@@ -36,6 +36,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
+#include <type_traits>
 
 #include "fs_internal.h"
 #include "fs_tables.h"
@@ -2152,6 +2153,18 @@ __device__ __forceinline__ void fast_rows(Lane& L, const StepParams& p, bool rea
   else row_loop<C>(L, p, reads, own, row_mul, a, row0, row1);
 }
 
+// A lane's state in and out, position.y with it in a general-geometry tick.
+template <class C>
+__device__ __forceinline__ void load_lane_y(Lane& L, const DevState& st, int a, uint32_t k) {
+  load_lane<C::P2>(L, st, a, k);
+  if constexpr (C::GEOM) L.f.y = reinterpret_cast<const float*>(st.posy)[2 * a + (int)k];
+}
+template <class C>
+__device__ __forceinline__ void store_lane_y(const Lane& L, const DevState& st, int a, uint32_t k) {
+  store_lane<C::P2>(L, st, a);
+  if constexpr (C::GEOM) reinterpret_cast<float*>(st.posy)[2 * a + (int)k] = L.f.y;
+}
+
 // One fused launch over all arenas (k_step_n*, the rollout: state stays in registers between the
 // p.n_steps ticks); the one-tick launch is step_one below.
 // HASH (kHashed) draws the actions in-kernel from splitmix64 instead of reading action rows.
@@ -2186,8 +2199,7 @@ __device__ __forceinline__ void step_body(const StepParams& p) {
   };
   // the arena state and the first action are in flight while the block stages the tables
   Lane L;
-  load_lane<P2>(L, p.st, a, k);
-  if constexpr (GEOM) L.f.y = reinterpret_cast<const float*>(p.st.posy)[2 * a + (int)k];
+  load_lane_y<C>(L, p.st, a, k);
   // the fused loop's rows: every lane loads (so the in-flight register is written by the load
   // alone); a lane without a row of its own reads P1's row 0, always valid in these launches,
   // and ignores it.  Rows 0 and 1 are both in flight while the block stages the tables.
@@ -2212,7 +2224,7 @@ __device__ __forceinline__ void step_body(const StepParams& p) {
   if constexpr (POL) stage_policy(p.pol);
   stage_tables<P2 == FS_P2_BOT || P2 == kActors, kFastLoops && kParserTable>();
   if constexpr (POL) {
-    if ((l & ~63) >= 2 * p.n_envs) return;  // the whole wave is past the last arena
+    if ((l & ~63) >= 2 * p.n_envs) return;  // the whole wave is past the last arena (as the actor bodies)
   } else {
     if (!active) return;
   }
@@ -2272,10 +2284,7 @@ __device__ __forceinline__ void step_body(const StepParams& p) {
       else row_loop<C>(L, p, reads, own, row_mul, a, row0, row1_rd);
     }
   }
-  if (active) {
-    store_lane<P2>(L, p.st, a);
-    if constexpr (GEOM) reinterpret_cast<float*>(p.st.posy)[2 * a + (int)k] = L.f.y;
-  }
+  if (active) store_lane_y<C>(L, p.st, a, k);
 }
 
 // The one-tick launch (fs_step, fs_step_masked: the VectorEnv.step path).  Nothing is amortized
@@ -2428,6 +2437,42 @@ __device__ __forceinline__ bool is_skippable(const Lane& L) {
 }
 
 __shared__ double sSkipReward[kBlock];  // each lane's reward of the tick it just ran
+
+// What the bodies below share (with load_lane_y / store_lane_y above step_body).  Each use is held to
+// DESIGN.md "The identity rule": a body where a helper compiled differently keeps its statements written
+// out, with a remark.
+
+// The reward row whose element r is the LDS slot `slot` (this lane's of sSkipReward): a flat address
+// computed in integers and made opaque, so the tick's store and the loop's read back are the same kind of
+// access to the same address; the tick adds 8 r back.
+__device__ __forceinline__ double* reward_slot_row(uintptr_t slot, uint32_t r) {
+  uintptr_t row = slot - 8ull * r;
+  asm volatile("" : "+v"(row));
+  return reinterpret_cast<double*>(row);
+}
+
+// A sampled index with Left (1) and Right (2) exchanged: the game input of a P2 that plays from its own
+// side (rollout.swap_left_right).
+__device__ __forceinline__ uint32_t swap_left_right(uint32_t m) { return (m & 4u) | ((m & 1u) << 1) | ((m >> 1) & 1u); }
+
+// A lane of an actor launch.  Lanes past the last arena stay in for the actor, whose MFMAs and lane
+// exchanges need the whole wave, on a copy of arena 0 that they never tick or store; a wholly idle wave
+// leaves behind the block's staging.
+struct ActorLane {
+  int l;              // the lane of the launch
+  bool active;        // it has an arena
+  int a;              // the arena (0: inactive)
+  uint32_t k;         // the fighter
+};
+__device__ __forceinline__ ActorLane actor_lane(const StepParams& p) {
+  ActorLane A;
+  A.l = blockIdx.x * kBlock + threadIdx.x;
+  A.active = A.l < 2 * p.n_envs;
+  A.a = A.active ? A.l >> 1 : 0;
+  A.k = A.l & 1;
+  return A;
+}
+
 template <class C>
 __device__ __forceinline__ void skip_body(const SkipParams& q) {
   constexpr int P2 = C::P2;
@@ -2438,8 +2483,7 @@ __device__ __forceinline__ void skip_body(const SkipParams& q) {
   const int a = in_range ? l >> 1 : 0;
   const uint32_t k = l & 1;
   Lane L;
-  load_lane<P2>(L, p.st, a, k);
-  if constexpr (C::GEOM) L.f.y = reinterpret_cast<const float*>(p.st.posy)[2 * a + (int)k];
+  load_lane_y<C>(L, p.st, a, k);
   const uint32_t on = p.active ? p.active[a] : 1u;
   uint32_t in = 0;
   double acc = 0.0;
@@ -2453,13 +2497,8 @@ __device__ __forceinline__ void skip_body(const SkipParams& q) {
   stage_tables<P2 == FS_P2_BOT>();
   if (!in_range || !on) return;
   L.te = next_tick_entry<false>(L.f);
-  // the tick's reward row: arena a's element is this lane's slot of sSkipReward (a flat address
-  // computed in integers and made opaque, so the tick's store and the read below are the same kind
-  // of access to the same address; the tick adds 8 a back)
-  uintptr_t row = reinterpret_cast<uintptr_t>(&sSkipReward[threadIdx.x]) - 8ull * (uint32_t)a;
-  asm volatile("" : "+v"(row));
-  StepParams ps = p;
-  ps.out.reward = reinterpret_cast<double*>(row);
+  StepParams ps = p;  // (the tick's reward row: arena a's element is this lane's slot)
+  ps.out.reward = reward_slot_row(reinterpret_cast<uintptr_t>(&sSkipReward[threadIdx.x]), (uint32_t)a);
   uint32_t none = 0;
   int ran = 0;
   bool more;
@@ -2471,8 +2510,7 @@ __device__ __forceinline__ void skip_body(const SkipParams& q) {
     in = 0;
     more = is_skippable(L) && !L.pending;
   } while (more && ran < q.max_ticks);
-  store_lane<P2>(L, p.st, a);
-  if constexpr (C::GEOM) reinterpret_cast<float*>(p.st.posy)[2 * a + (int)k] = L.f.y;
+  store_lane_y<C>(L, p.st, a, k);
   // one add per wave for its arenas still pending (the lanes of the wave meet again here)
   const uint64_t still = __builtin_amdgcn_ballot_w64(more && k == 0);
   if (k == 0) {
@@ -2498,8 +2536,7 @@ __global__ __launch_bounds__(256) void k_step_skip(SkipParams q) {
 // (ds_bpermute exchanges and MFMAs), so the loop is over decisions: the converged wave samples one
 // action per arena from the arena's observation as it stands, each pair then runs the tick that
 // takes it and skips on with input 0 on its own test, and the wave meets again behind the pair
-// loop -- the actor is paid once per decision, not per tick.  Lanes past the last arena stay in
-// for the actor (on a copy of arena 0 that they never tick or store), a wholly idle wave leaves.
+// loop -- the actor is paid once per decision, not per tick (the lanes: ActorLane).
 // `max_ticks` closes a decision (flagged in capped_out): an arena still skippable there starts an
 // ordinary decision next, so nothing but the arena state carries over between launches, and the
 // host may split a call into launches at any decision.  Row d * N + i of every output is arena
@@ -2515,19 +2552,16 @@ __device__ __forceinline__ void skip_policy_body(const SkipPolicyParams& q) {
   static_assert(C::TP == kTabLds && (P2 == FS_P2_BOT || P2 == FS_P2_NOOP || P2 == kActors),
                 "fs_step_skip_policy: the bot or an idle P2");
   const StepParams& p = q.p;
-  const int l = blockIdx.x * kBlock + threadIdx.x;
-  const bool active = l < 2 * p.n_envs;
-  const int a = active ? l >> 1 : 0;
-  const uint32_t k = l & 1;
+  const ActorLane A = actor_lane(p);
   Lane L;
-  load_lane<P2>(L, p.st, a, k);
-  if constexpr (C::GEOM) L.f.y = reinterpret_cast<const float*>(p.st.posy)[2 * a + (int)k];
+  load_lane_y<C>(L, p.st, A.a, A.k);
   stage_policy(p.pol);
   stage_tables<P2 == FS_P2_BOT || P2 == kActors>();
-  if ((l & ~63) >= 2 * p.n_envs) return;  // the whole wave is past the last arena
+  // (the exit test, row_step and arena0 written out in each body: deliberate, DESIGN.md "The identity rule")
+  if ((A.l & ~63) >= 2 * p.n_envs) return;  // the whole wave is past the last arena
   L.te = next_tick_entry<false>(L.f);
   const uint32_t row_step = (uint32_t)p.out_stride_steps * (uint32_t)p.n_envs;
-  const uint32_t arena0 = (uint32_t)(l & ~63) >> 1;
+  const uint32_t arena0 = (uint32_t)(A.l & ~63) >> 1;
   const uintptr_t slot = reinterpret_cast<uintptr_t>(&sSkipReward[threadIdx.x]);
   StepParams ps = p;
   uint32_t none = 0;
@@ -2536,12 +2570,9 @@ __device__ __forceinline__ void skip_policy_body(const SkipPolicyParams& q) {
     policy_features(L, d0, d1);
     const PolicyWeights W = policy_weights();
     const PolicyOut po = policy_act(W, d0, d1, p.pol.seed, p.arena_base + arena0, p.t0 + (uint64_t)d);
-    if (active) {
-      const uint32_t r = (uint32_t)d * row_step + (uint32_t)a;  // the decision's output row
-      // the ticks' reward row: element r is this lane's slot of LDS (skip_body)
-      uintptr_t row = slot - 8ull * r;
-      asm volatile("" : "+v"(row));
-      ps.out.reward = reinterpret_cast<double*>(row);
+    if (A.active) {
+      const uint32_t r = (uint32_t)d * row_step + (uint32_t)A.a;  // the decision's output row
+      ps.out.reward = reward_slot_row(slot, r);
       uint32_t in = po.action;
       double acc = 0.0;
       int ran = 0;
@@ -2553,8 +2584,8 @@ __device__ __forceinline__ void skip_policy_body(const SkipPolicyParams& q) {
         in = 0;
         more = is_skippable(L) && !L.pending;
       } while (more && ran < q.max_ticks);
-      if (k == 0) {
-        const uint32_t row_d = (uint32_t)d * (uint32_t)p.n_envs + (uint32_t)a;
+      if (A.k == 0) {  // (the stores that close a decision, as in skip_selfplay_body: deliberate, DESIGN.md "The identity rule")
+        const uint32_t row_d = (uint32_t)d * (uint32_t)p.n_envs + (uint32_t)A.a;
         p.out.reward[r] = acc;
         if (p.pol.actions) p.pol.actions[row_d] = (uint8_t)po.action;
         if (p.pol.logp) p.pol.logp[row_d] = po.logp;
@@ -2563,10 +2594,7 @@ __device__ __forceinline__ void skip_policy_body(const SkipPolicyParams& q) {
       }
     }
   }
-  if (active) {
-    store_lane<P2>(L, p.st, a);
-    if constexpr (C::GEOM) reinterpret_cast<float*>(p.st.posy)[2 * a + (int)k] = L.f.y;
-  }
+  if (A.active) store_lane_y<C>(L, p.st, A.a, A.k);
 }
 
 // (the general-geometry tick behind a launch-uniform branch, as in k_step_n)
@@ -2585,8 +2613,7 @@ __global__ __launch_bounds__(256) void k_step_skip_policy(SkipPolicyParams q) {
 // the same counter.  Lane 2a + k stores actor k's sample of arena a.
 // P1's 17 weight fragments stay in registers as in k_step_n_policy (239 VGPRs there); P2's are
 // read from a second LDS image every tick (PolicyWeightsLds): a second resident set would end two
-// waves per SIMD, which 65 536 arenas are.  Lanes past the last arena stay in for the actors, a
-// wholly idle wave leaves (as POL).
+// waves per SIMD, which 65 536 arenas are.
 // POOL (k_step_n_selfplay_pool): P2's image is staged from the block's slot of `pool` (pool_policy), i.e.
 // per FS_SELFPLAY_GROUP arenas; nothing after the staging differs.
 template <class C, bool POOL = false>
@@ -2594,32 +2621,30 @@ __device__ __forceinline__ void selfplay_body(const SelfPlayParams& q, const Poo
   constexpr int P2 = C::P2;
   static_assert(C::TP == kTabLds && P2 == FS_P2_EXTERNAL, "fs_step_n_selfplay: a remote P2, played by the second actor");
   const StepParams& p = q.p;
-  const int l = blockIdx.x * kBlock + threadIdx.x;
-  const bool active = l < 2 * p.n_envs;
-  const int a = active ? l >> 1 : 0;
-  const uint32_t k = l & 1;
+  const ActorLane A = actor_lane(p);
   Lane L;
-  load_lane<P2>(L, p.st, a, k);
-  if constexpr (C::GEOM) L.f.y = reinterpret_cast<const float*>(p.st.posy)[2 * a + (int)k];
+  load_lane_y<C>(L, p.st, A.a, A.k);
   stage_policy(p.pol);
+  // (P2's image, staged alike in both self-play bodies: deliberate, DESIGN.md "The identity rule")
   if constexpr (POOL) {
     if (threadIdx.x >= 64 && threadIdx.x < 128) stage_policy<true>(pool_policy(q.pol2, pool), sPol2);
   } else {
     stage_policy<true>(q.pol2, sPol2);
   }
   stage_tables<false>();
-  if ((l & ~63) >= 2 * p.n_envs) return;  // the whole wave is past the last arena
+  // (the exit test, row_step and arena0 written out in each body: deliberate, DESIGN.md "The identity rule")
+  if ((A.l & ~63) >= 2 * p.n_envs) return;  // the whole wave is past the last arena
   L.te = next_tick_entry<false>(L.f);
   const uint32_t row_step = (uint32_t)p.out_stride_steps * (uint32_t)p.n_envs;
-  const uint32_t arena0 = (uint32_t)(l & ~63) >> 1;
+  const uint32_t arena0 = (uint32_t)(A.l & ~63) >> 1;
   const uint32_t mir = q.mirror ? 1u : 0u;
   // this lane's actor's sample arrays (selected in registers, not per lane on the argument struct)
   uint8_t* const act1 = p.pol.actions;
   uint8_t* const act2 = q.pol2.actions;
   float* const lp1 = p.pol.logp;
   float* const lp2 = q.pol2.logp;
-  uint8_t* const act_out = k == 0 ? act1 : act2;
-  float* const logp_out = k == 0 ? lp1 : lp2;
+  uint8_t* const act_out = A.k == 0 ? act1 : act2;
+  float* const logp_out = A.k == 0 ? lp1 : lp2;
   uint32_t d0, d1;
   policy_features(L, d0, d1);
   const PolicyWeights W = policy_weights();
@@ -2630,21 +2655,17 @@ __device__ __forceinline__ void selfplay_body(const SelfPlayParams& q, const Poo
     if (p.prio) prio_slice(grp);
     const PolicyOut po1 = policy_act(W, d0, d1, p.pol.seed, p.arena_base + arena0, p.t0 + (uint64_t)t);
     const PolicyOut po2 = policy_act_side(W2.fresh(), d0, d1, q.pol2.seed, p.arena_base + arena0, p.t0 + (uint64_t)t, mir);
-    if (active) {
-      const uint32_t row = (uint32_t)t * (uint32_t)p.n_envs + (uint32_t)a;
-      const uint32_t mine = k == 0 ? po1.action : po2.action;
+    if (A.active) {
+      const uint32_t row = (uint32_t)t * (uint32_t)p.n_envs + (uint32_t)A.a;
+      const uint32_t mine = A.k == 0 ? po1.action : po2.action;
       if (act_out) act_out[row] = (uint8_t)mine;
-      if (logp_out) logp_out[row] = k == 0 ? po1.logp : po2.logp;
-      // P2's game input: Left (1) and Right (2) exchanged when it plays from its own side
-      const uint32_t flipped = (mine & 4u) | ((mine & 1u) << 1) | ((mine >> 1) & 1u);
-      env_step<FS_TICK(C)>(L, (k & mir) ? flipped : mine, p, (uint32_t)t * row_step + (uint32_t)a, none);
+      if (logp_out) logp_out[row] = A.k == 0 ? po1.logp : po2.logp;
+      // (P2's game input when it plays from its own side)
+      env_step<FS_TICK(C)>(L, (A.k & mir) ? swap_left_right(mine) : mine, p, (uint32_t)t * row_step + (uint32_t)A.a, none);
     }
     policy_features(L, d0, d1);
   }
-  if (active) {
-    store_lane<P2>(L, p.st, a);
-    if constexpr (C::GEOM) reinterpret_cast<float*>(p.st.posy)[2 * a + (int)k] = L.f.y;
-  }
+  if (A.active) store_lane_y<C>(L, p.st, A.a, A.k);
 }
 
 // (the general-geometry tick behind a launch-uniform branch, as in k_step_n)
@@ -2690,24 +2711,22 @@ __device__ __forceinline__ void skip_selfplay_body(const SkipSelfPlayParams& q, 
   constexpr int P2 = C::P2;
   static_assert(C::TP == kTabLds && P2 == FS_P2_EXTERNAL, "fs_step_skip_selfplay: a remote P2, played by the second actor");
   const StepParams& p = q.p;
-  const int l = blockIdx.x * kBlock + threadIdx.x;
-  const bool active = l < 2 * p.n_envs;
-  const int a = active ? l >> 1 : 0;
-  const uint32_t k = l & 1;
+  const ActorLane A = actor_lane(p);
   Lane L;
-  load_lane<P2>(L, p.st, a, k);
-  if constexpr (C::GEOM) L.f.y = reinterpret_cast<const float*>(p.st.posy)[2 * a + (int)k];
+  load_lane_y<C>(L, p.st, A.a, A.k);
   stage_policy(p.pol);
+  // (P2's image, staged alike in both self-play bodies: deliberate, DESIGN.md "The identity rule")
   if constexpr (POOL) {
     if (threadIdx.x >= 64 && threadIdx.x < 128) stage_policy<true>(pool_policy(q.pol2, pool), sPol2);
   } else {
     stage_policy<true>(q.pol2, sPol2);
   }
   stage_tables<false>();
-  if ((l & ~63) >= 2 * p.n_envs) return;  // the whole wave is past the last arena
+  // (the exit test, row_step and arena0 written out in each body: deliberate, DESIGN.md "The identity rule")
+  if ((A.l & ~63) >= 2 * p.n_envs) return;  // the whole wave is past the last arena
   L.te = next_tick_entry<false>(L.f);
   const uint32_t row_step = (uint32_t)p.out_stride_steps * (uint32_t)p.n_envs;
-  const uint32_t arena0 = (uint32_t)(l & ~63) >> 1;
+  const uint32_t arena0 = (uint32_t)(A.l & ~63) >> 1;
   const uint32_t mir = q.mirror ? 1u : 0u;
   const uint32_t max_ticks = (uint32_t)q.max_ticks;
   const uintptr_t slot = reinterpret_cast<uintptr_t>(&sSkipReward[threadIdx.x]);
@@ -2715,7 +2734,7 @@ __device__ __forceinline__ void skip_selfplay_body(const SkipSelfPlayParams& q, 
   const PolicyWeightsLds W2 = policy_weights_lds(sPol2);
   StepParams ps = p;
   uint32_t none = 0;
-  const uint32_t n = active ? (uint32_t)p.n_steps : 0u;  // (a lane past the last arena has no decision to run)
+  const uint32_t n = A.active ? (uint32_t)p.n_steps : 0u;  // (a lane past the last arena has no decision to run)
   uint32_t d = 0, j = 0;
   double acc = 0.0;
   bool boundary = true;
@@ -2736,17 +2755,17 @@ __device__ __forceinline__ void skip_selfplay_body(const SkipSelfPlayParams& q, 
       lp1 = po1.logp;
     }
     if (d < n) {
-      const uint32_t r = d * row_step + (uint32_t)a;  // the decision's output row
-      // the ticks' reward row: element r is this lane's slot of LDS (skip_body)
+      const uint32_t r = d * row_step + (uint32_t)A.a;  // the decision's output row
+      // the ticks' reward row (not reward_slot_row: deliberate, DESIGN.md "The identity rule")
       uintptr_t row = slot - 8ull * r;
       asm volatile("" : "+v"(row));
       ps.out.reward = reinterpret_cast<double*>(row);
       uint32_t in = boundary ? a1 : 0u;
-      if (k) {
-        const uint32_t s = (d * max_ticks + j) * (uint32_t)p.n_envs + (uint32_t)a;
+      if (A.k) {
+        const uint32_t s = (d * max_ticks + j) * (uint32_t)p.n_envs + (uint32_t)A.a;
         if (q.pol2.actions) q.pol2.actions[s] = (uint8_t)po2.action;
         if (q.pol2.logp) q.pol2.logp[s] = po2.logp;
-        // P2's game input: Left (1) and Right (2) exchanged when it plays from its own side
+        // P2's game input when it plays from its own side (not swap_left_right: deliberate, DESIGN.md "The identity rule")
         const uint32_t flipped = (po2.action & 4u) | ((po2.action & 1u) << 1) | ((po2.action >> 1) & 1u);
         in = mir ? flipped : po2.action;
       }
@@ -2756,8 +2775,8 @@ __device__ __forceinline__ void skip_selfplay_body(const SkipSelfPlayParams& q, 
       boundary = false;
       const bool more = is_skippable(L) && !L.pending;
       if (!more || j == max_ticks) {
-        if (k == 0) {
-          const uint32_t row_d = d * (uint32_t)p.n_envs + (uint32_t)a;
+        if (A.k == 0) {  // (as in skip_policy_body: deliberate, DESIGN.md "The identity rule")
+          const uint32_t row_d = d * (uint32_t)p.n_envs + (uint32_t)A.a;
           p.out.reward[r] = acc;
           if (p.pol.actions) p.pol.actions[row_d] = (uint8_t)a1;
           if (p.pol.logp) p.pol.logp[row_d] = lp1;
@@ -2772,10 +2791,7 @@ __device__ __forceinline__ void skip_selfplay_body(const SkipSelfPlayParams& q, 
     }
     policy_features(L, d0, d1);
   }
-  if (active) {
-    store_lane<P2>(L, p.st, a);
-    if constexpr (C::GEOM) reinterpret_cast<float*>(p.st.posy)[2 * a + (int)k] = L.f.y;
-  }
+  if (A.active) store_lane_y<C>(L, p.st, A.a, A.k);
 }
 
 // (the general-geometry tick behind a launch-uniform branch, as in k_step_n; in the selfplay namespace
@@ -2812,19 +2828,16 @@ template <class C>
 __device__ __forceinline__ void league_bot_body(const StepParams& p) {
   constexpr int P2 = C::P2;
   static_assert(C::TP == kTabLds && P2 == kActors && C::KIND == kPolicy, "fs_step_n_league: a bot group");
-  const int l = blockIdx.x * kBlock + threadIdx.x;
-  const bool active = l < 2 * p.n_envs;
-  const int a = active ? l >> 1 : 0;
-  const uint32_t k = l & 1;
+  const ActorLane A = actor_lane(p);
   Lane L;
-  load_lane<P2>(L, p.st, a, k);
-  if constexpr (C::GEOM) L.f.y = reinterpret_cast<const float*>(p.st.posy)[2 * a + (int)k];
+  load_lane_y<C>(L, p.st, A.a, A.k);
   stage_policy(p.pol);
   stage_tables<true>();
-  if ((l & ~63) >= 2 * p.n_envs) return;  // the whole wave is past the last arena
+  // (the exit test, row_step and arena0 written out in each body: deliberate, DESIGN.md "The identity rule")
+  if ((A.l & ~63) >= 2 * p.n_envs) return;  // the whole wave is past the last arena
   L.te = next_tick_entry<false>(L.f);
   const uint32_t row_step = (uint32_t)p.out_stride_steps * (uint32_t)p.n_envs;
-  const uint32_t arena0 = (uint32_t)(l & ~63) >> 1;
+  const uint32_t arena0 = (uint32_t)(A.l & ~63) >> 1;
   uint32_t d0, d1;
   policy_features(L, d0, d1);
   const PolicyWeights W = policy_weights();
@@ -2833,21 +2846,18 @@ __device__ __forceinline__ void league_bot_body(const StepParams& p) {
   for (int t = 0; t < p.n_steps; t++) {
     if (p.prio) prio_slice(grp);
     const PolicyOut po = policy_act(W, d0, d1, p.pol.seed, p.arena_base + arena0, p.t0 + (uint64_t)t);
-    if (active) {
-      const uint32_t row = (uint32_t)t * (uint32_t)p.n_envs + (uint32_t)a;
-      if (k == 0) {
+    if (A.active) {
+      const uint32_t row = (uint32_t)t * (uint32_t)p.n_envs + (uint32_t)A.a;
+      if (A.k == 0) {
         if (p.pol.actions) p.pol.actions[row] = (uint8_t)po.action;
         if (p.pol.logp) p.pol.logp[row] = po.logp;
       }
       // (P2's lane: the bot's stored input plays, and its stale remote input stays as it is)
-      env_step<FS_TICK(C)>(L, k == 0 ? po.action : 0u, p, (uint32_t)t * row_step + (uint32_t)a, none);
+      env_step<FS_TICK(C)>(L, A.k == 0 ? po.action : 0u, p, (uint32_t)t * row_step + (uint32_t)A.a, none);
     }
     policy_features(L, d0, d1);
   }
-  if (active) {
-    store_lane<P2>(L, p.st, a);
-    if constexpr (C::GEOM) reinterpret_cast<float*>(p.st.posy)[2 * a + (int)k] = L.f.y;
-  }
+  if (A.active) store_lane_y<C>(L, p.st, A.a, A.k);
 }
 
 // (a namespace of its own, as fsk::selfplay: that one holds exactly its four kernels)
@@ -3242,20 +3252,28 @@ static void launch_step_p2(const StepParams& p_in, hipStream_t s) {
 #undef FS_LAUNCH
 }
 
-template <int FM>
-static hipError_t launch_step_fm(const StepParams& p, int variant, hipStream_t s) {
-  switch (variant) {
-    case FS_P2_EXTERNAL: launch_step_p2<FM, FS_P2_EXTERNAL>(p, s); break;
-    case FS_P2_BOT: launch_step_p2<FM, FS_P2_BOT>(p, s); break;
-    case kActors: launch_step_p2<FM, kActors>(p, s); break;
-    default: launch_step_p2<FM, FS_P2_NOOP>(p, s); break;
-  }
+// A launch in the handle's float model: `launch(fm)` names the kernel with fm() as its FM.  FS_FLOAT_DOUBLE's
+// instance is named first (the device code numbers the kernels in the order the host names them).
+template <class F>
+static hipError_t launch_fm(int float_mode, F launch) {
+  if (float_mode == FS_FLOAT_DOUBLE) launch(std::integral_constant<int, FS_FLOAT_DOUBLE>{});
+  else launch(std::integral_constant<int, FS_FLOAT_STRICT32>{});
   return hipGetLastError();
 }
+// the same for a kernel template K<FM> on `grid` blocks with its one parameter struct (a braced
+// temporary goes in parentheses, `(Params{a, b})`: its comma would otherwise split the macro's argument)
+#define FS_LAUNCH_FM(K, float_mode, grid, s, q) \
+  launch_fm(float_mode, [&](auto fm) { hipLaunchKernelGGL(K<fm()>, grid, dim3(kBlock), 0, s, q); })
 
 hipError_t launch_step(const StepParams& p, int float_mode, int variant, hipStream_t s) {
-  return float_mode == FS_FLOAT_DOUBLE ? launch_step_fm<FS_FLOAT_DOUBLE>(p, variant, s)
-                                       : launch_step_fm<FS_FLOAT_STRICT32>(p, variant, s);
+  return launch_fm(float_mode, [&](auto fm) {
+    switch (variant) {
+      case FS_P2_EXTERNAL: launch_step_p2<fm(), FS_P2_EXTERNAL>(p, s); break;
+      case FS_P2_BOT: launch_step_p2<fm(), FS_P2_BOT>(p, s); break;
+      case kActors: launch_step_p2<fm(), kActors>(p, s); break;
+      default: launch_step_p2<fm(), FS_P2_NOOP>(p, s); break;
+    }
+  });
 }
 
 // The kernel launch_step_p2 runs for a launch of this shape, as rocprofv3 names it (fs_step_kernel).
@@ -3268,11 +3286,7 @@ const char* step_kernel_name(bool policy, bool hashed, int n_steps, int n_envs, 
 }
 
 hipError_t launch_reset(const ResetParams& p, int float_mode, hipStream_t s) {
-  if (float_mode == FS_FLOAT_DOUBLE)
-    hipLaunchKernelGGL(k_reset<FS_FLOAT_DOUBLE>, grid_for(2 * p.n_envs), dim3(kBlock), 0, s, p);
-  else
-    hipLaunchKernelGGL(k_reset<FS_FLOAT_STRICT32>, grid_for(2 * p.n_envs), dim3(kBlock), 0, s, p);
-  return hipGetLastError();
+  return FS_LAUNCH_FM(k_reset, float_mode, grid_for(2 * p.n_envs), s, p);
 }
 
 hipError_t launch_set_p2(const DevState& st, int bot, const uint8_t* mask, int n, hipStream_t s) {
@@ -3298,33 +3312,23 @@ hipError_t launch_set_state(const DevState& st, const fs_arena_state* src, int n
   return hipGetLastError();
 }
 
-// (named last: the device code numbers the kernels in the order the host first names them, and the
-// step kernels keep their numbers -- DESIGN.md "The identity rule")
-template <int FM>
-static void launch_step_skip_fm(const SkipParams& q, int p2_mode, hipStream_t s) {
-  const dim3 grid = grid_for(2 * q.p.n_envs), block(kBlock);
-  if (p2_mode == FS_P2_BOT) hipLaunchKernelGGL((k_step_skip<FM, FS_P2_BOT>), grid, block, 0, s, q);
-  else hipLaunchKernelGGL((k_step_skip<FM, FS_P2_NOOP>), grid, block, 0, s, q);
-}
-
+// The launches below name their kernels after every other, in this order: the device code numbers the
+// kernels in the order the host first names them, and the step kernels keep their numbers (DESIGN.md "The
+// identity rule").  Within a launch: the float model, then P2 (bot, idle) or the pool form first.
 hipError_t launch_step_skip(const SkipParams& q, int float_mode, int p2_mode, hipStream_t s) {
-  if (float_mode == FS_FLOAT_DOUBLE) launch_step_skip_fm<FS_FLOAT_DOUBLE>(q, p2_mode, s);
-  else launch_step_skip_fm<FS_FLOAT_STRICT32>(q, p2_mode, s);
-  return hipGetLastError();
-}
-
-// (named after every other kernel, like k_step_skip above)
-template <int FM>
-static void launch_step_skip_policy_fm(const SkipPolicyParams& q, int p2_mode, hipStream_t s) {
   const dim3 grid = grid_for(2 * q.p.n_envs), block(kBlock);
-  if (p2_mode == FS_P2_BOT) hipLaunchKernelGGL((k_step_skip_policy<FM, FS_P2_BOT>), grid, block, 0, s, q);
-  else hipLaunchKernelGGL((k_step_skip_policy<FM, FS_P2_NOOP>), grid, block, 0, s, q);
+  return launch_fm(float_mode, [&](auto fm) {
+    if (p2_mode == FS_P2_BOT) hipLaunchKernelGGL((k_step_skip<fm(), FS_P2_BOT>), grid, block, 0, s, q);
+    else hipLaunchKernelGGL((k_step_skip<fm(), FS_P2_NOOP>), grid, block, 0, s, q);
+  });
 }
 
 hipError_t launch_step_skip_policy(const SkipPolicyParams& q, int float_mode, int p2_mode, hipStream_t s) {
-  if (float_mode == FS_FLOAT_DOUBLE) launch_step_skip_policy_fm<FS_FLOAT_DOUBLE>(q, p2_mode, s);
-  else launch_step_skip_policy_fm<FS_FLOAT_STRICT32>(q, p2_mode, s);
-  return hipGetLastError();
+  const dim3 grid = grid_for(2 * q.p.n_envs), block(kBlock);
+  return launch_fm(float_mode, [&](auto fm) {
+    if (p2_mode == FS_P2_BOT) hipLaunchKernelGGL((k_step_skip_policy<fm(), FS_P2_BOT>), grid, block, 0, s, q);
+    else hipLaunchKernelGGL((k_step_skip_policy<fm(), FS_P2_NOOP>), grid, block, 0, s, q);
+  });
 }
 
 const char* step_skip_policy_kernel_name(int float_mode, int p2_mode) {
@@ -3333,22 +3337,17 @@ const char* step_skip_policy_kernel_name(int float_mode, int p2_mode) {
   return buf;
 }
 
-// (named after every other kernel; the wave-priority slices as launch_choice sets them for k_step_n_policy)
+// the wave-priority slices of a self-play or league tick launch: as launch_choice sets them for k_step_n_policy
+static bool actor_prio(const StepParams& p) {
+  return launch_choice(true, false, p.n_steps, p.n_envs, FS_P2_EXTERNAL, p.geom != 0, false, p.autoreset_mode).prio;
+}
+
 hipError_t launch_step_selfplay(const SelfPlayParams& q_in, const PoolParams* pool, int float_mode, hipStream_t s) {
-  const StepParams& p = q_in.p;
   SelfPlayParams q = q_in;
-  q.p.prio = launch_choice(true, false, p.n_steps, p.n_envs, FS_P2_EXTERNAL, p.geom != 0, false, p.autoreset_mode).prio;
-  const dim3 grid = grid_for(2 * p.n_envs), block(kBlock);
-  if (pool) {
-    const SelfPlayPoolParams qp{q, *pool};
-    if (float_mode == FS_FLOAT_DOUBLE) hipLaunchKernelGGL(selfplay::k_step_n_selfplay_pool<FS_FLOAT_DOUBLE>, grid, block, 0, s, qp);
-    else hipLaunchKernelGGL(selfplay::k_step_n_selfplay_pool<FS_FLOAT_STRICT32>, grid, block, 0, s, qp);
-  } else if (float_mode == FS_FLOAT_DOUBLE) {
-    hipLaunchKernelGGL(selfplay::k_step_n_selfplay<FS_FLOAT_DOUBLE>, grid, block, 0, s, q);
-  } else {
-    hipLaunchKernelGGL(selfplay::k_step_n_selfplay<FS_FLOAT_STRICT32>, grid, block, 0, s, q);
-  }
-  return hipGetLastError();
+  q.p.prio = actor_prio(q.p);
+  const dim3 grid = grid_for(2 * q.p.n_envs);
+  if (pool) return FS_LAUNCH_FM(selfplay::k_step_n_selfplay_pool, float_mode, grid, s, (SelfPlayPoolParams{q, *pool}));
+  return FS_LAUNCH_FM(selfplay::k_step_n_selfplay, float_mode, grid, s, q);
 }
 
 const char* step_selfplay_kernel_name(int float_mode, bool pool) {
@@ -3357,19 +3356,10 @@ const char* step_selfplay_kernel_name(int float_mode, bool pool) {
   return buf;
 }
 
-// (named after every other kernel)
 hipError_t launch_step_skip_selfplay(const SkipSelfPlayParams& q, const PoolParams* pool, int float_mode, hipStream_t s) {
-  const dim3 grid = grid_for(2 * q.p.n_envs), block(kBlock);
-  if (pool) {
-    const SkipSelfPlayPoolParams qp{q, *pool};
-    if (float_mode == FS_FLOAT_DOUBLE) hipLaunchKernelGGL(selfplay::k_step_skip_pool_selfplay<FS_FLOAT_DOUBLE>, grid, block, 0, s, qp);
-    else hipLaunchKernelGGL(selfplay::k_step_skip_pool_selfplay<FS_FLOAT_STRICT32>, grid, block, 0, s, qp);
-  } else if (float_mode == FS_FLOAT_DOUBLE) {
-    hipLaunchKernelGGL(selfplay::k_step_skip_selfplay<FS_FLOAT_DOUBLE>, grid, block, 0, s, q);
-  } else {
-    hipLaunchKernelGGL(selfplay::k_step_skip_selfplay<FS_FLOAT_STRICT32>, grid, block, 0, s, q);
-  }
-  return hipGetLastError();
+  const dim3 grid = grid_for(2 * q.p.n_envs);
+  if (pool) return FS_LAUNCH_FM(selfplay::k_step_skip_pool_selfplay, float_mode, grid, s, (SkipSelfPlayPoolParams{q, *pool}));
+  return FS_LAUNCH_FM(selfplay::k_step_skip_selfplay, float_mode, grid, s, q);
 }
 
 const char* step_skip_selfplay_kernel_name(int float_mode, bool pool) {
@@ -3378,23 +3368,15 @@ const char* step_skip_selfplay_kernel_name(int float_mode, bool pool) {
   return buf;
 }
 
-// fs_step_n_league / fs_step_skip_league (named after every other kernel; launched as their pool twins are)
-hipError_t launch_step_league(const SelfPlayParams& q_in, const PoolParams& pool, int float_mode, hipStream_t s) {
-  const StepParams& p = q_in.p;
-  SelfPlayPoolParams qp{q_in, pool};
-  qp.q.p.prio = launch_choice(true, false, p.n_steps, p.n_envs, FS_P2_EXTERNAL, p.geom != 0, false, p.autoreset_mode).prio;
-  const dim3 grid = grid_for(2 * p.n_envs), block(kBlock);
-  if (float_mode == FS_FLOAT_DOUBLE) hipLaunchKernelGGL(league::k_step_n_league<FS_FLOAT_DOUBLE>, grid, block, 0, s, qp);
-  else hipLaunchKernelGGL(league::k_step_n_league<FS_FLOAT_STRICT32>, grid, block, 0, s, qp);
-  return hipGetLastError();
+// fs_step_n_league / fs_step_skip_league: launched as their pool twins are
+hipError_t launch_step_league(const SelfPlayParams& q, const PoolParams& pool, int float_mode, hipStream_t s) {
+  SelfPlayPoolParams qp{q, pool};
+  qp.q.p.prio = actor_prio(q.p);
+  return FS_LAUNCH_FM(league::k_step_n_league, float_mode, grid_for(2 * q.p.n_envs), s, qp);
 }
 
 hipError_t launch_step_skip_league(const SkipSelfPlayParams& q, const PoolParams& pool, int float_mode, hipStream_t s) {
-  const dim3 grid = grid_for(2 * q.p.n_envs), block(kBlock);
-  const SkipSelfPlayPoolParams qp{q, pool};
-  if (float_mode == FS_FLOAT_DOUBLE) hipLaunchKernelGGL(league::k_step_skip_league<FS_FLOAT_DOUBLE>, grid, block, 0, s, qp);
-  else hipLaunchKernelGGL(league::k_step_skip_league<FS_FLOAT_STRICT32>, grid, block, 0, s, qp);
-  return hipGetLastError();
+  return FS_LAUNCH_FM(league::k_step_skip_league, float_mode, grid_for(2 * q.p.n_envs), s, (SkipSelfPlayPoolParams{q, pool}));
 }
 
 const char* step_league_kernel_name(int float_mode, bool skip) {
@@ -3402,5 +3384,6 @@ const char* step_league_kernel_name(int float_mode, bool skip) {
   snprintf(buf, sizeof buf, "fsk::league::k_step_%s_league<%d>", skip ? "skip" : "n", float_mode == FS_FLOAT_DOUBLE);
   return buf;
 }
+#undef FS_LAUNCH_FM
 
 }  // namespace fsk

@@ -11,7 +11,8 @@ labels, the .amdhsa_* block and the resource comments.  Labels an inline-asm sta
 behind one that gained or lost such a statement carries other numbers around the same bytes: they are
 renumbered per function, in order of appearance, before the comparison.  One line per function: the two instruction
 counts and `identical`, `differs`, or `only here` for a kernel one listing lacks (an added kernel changes
-none).  Exit status 1 if a step kernel (k_step*) of both listings differs: a refactor
+none).  A step kernel is a function named fsk::k_step*, fsk::selfplay::k_step* or fsk::league::k_step*.
+Exit status 1 if a step kernel of the parent differs in the tree or is missing there: a refactor
 of the tick must leave those byte for byte (DESIGN.md "The identity rule").
 """
 import re
@@ -43,6 +44,10 @@ def local_labels(text):
                   else "%s#%d" % (m.group(1), order.setdefault(m.group(2), len(order))), text, flags=re.M)
 
 
+def is_step_kernel(name):
+    return re.match(r"fsk::(?:selfplay::|league::)?k_step", name) is not None
+
+
 def count(text):
     return len(re.findall(r"^\t[a-z][a-z0-9_]*(?:\s|$)", text, re.M))
 
@@ -53,10 +58,10 @@ def main():
     print("# %-46s %8s %8s" % ("function", "parent", "tree"))
     for name in list(a) + [n for n in b if n not in a]:
         same = a.get(name) == b.get(name)
-        bad += (not same) and name in a and name.startswith("fsk::k_step")  # (a kernel the tree adds is no change)
+        bad += (not same) and name in a and is_step_kernel(name)  # (a kernel the tree adds is no change)
         print("%-48s %8s %8s  %s" % (name, count(a[name]) if name in a else "-", count(b[name]) if name in b else "-",
                                      "identical" if same else "differs" if name in a and name in b else "only here"))
-    steps = [n for n in a if n.startswith("fsk::k_step")]
+    steps = [n for n in a if is_step_kernel(n)]
     print("# %d functions, %d step kernels, %d step kernels differ" % (len(a), len(steps), bad))
     return 1 if bad else 0
 
